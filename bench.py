@@ -15,9 +15,11 @@ bytes with the same kernels (agc_hip_sample_pack_fasta) -- and whose archives ar
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line (rank 0).  `value` = bases of all ranks / max-over-ranks time.
-roofline.* is for the kernel with the largest time per step (every kernel of the path competes), timed with HIP
-events on the library's own stream, on the layout as built and on SURVEY 8d's 2-bit figures; cpu_baseline is the reference CPU implementation (oracle/_ref/agc, when it was
-prebuilt) or the oracle port, timed on this box's host cores on a bounded sample.
+A plain run does only what that line needs: setup, warm-up, the timed steps (+ Close), the line.  --full adds what the
+headline does not need: roofline.* -- for the kernel with the largest time per step (every kernel of the path competes), timed
+with HIP events on the library's own stream, on the layout as built and on SURVEY 8d's 2-bit figures -- and cpu_baseline, the
+reference CPU implementation (oracle/_ref/agc, when it was prebuilt) or the oracle port, timed on the host cores on a bounded sample.
+--dump-outputs DIR writes what the timed path produced (the archive: see dump_outputs) as DIR/*.npy after the timed steps.
 """
 import argparse
 import json
@@ -37,6 +39,11 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 K, MML, SEG, PACK = 31, 15, 60000, 100
+# sample slots resident in HBM at most (3.55 GiB each: FASTA bytes + packed buffers, beside the reference and the library's own
+# buffers).  Step s uses slot s % MAX_SAMPLE_SLOTS; from step MAX_SAMPLE_SLOTS on, a slot is refilled with step s's own sample
+# (its substitutions replace the ones of the slot's previous sample, inside the timed step: resample_slot), so every step compresses
+# a distinct sample and any --steps fits on one MI355X.  Runs of up to this many steps (warm-up included) are generated as always.
+MAX_SAMPLE_SLOTS = 48
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
 BYTES_PER_SYMBOL = 0.25  # the layout every kernel of the step reads: samples AND group references in 2-bit words (sym_view.h)
 
@@ -48,8 +55,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--gbp", type=float, default=3.0, help="bases per sample (Gbp)")
     ap.add_argument("--div", type=float, default=1e-3, help="per-base substitution rate")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel HIP-event times of the timed region (the roofline "
+                         "object) and the CPU baseline (cpu_baseline, unless --no-cpu-baseline).  Off: setup, warm-up, steps, the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path produced -- the archive (sha256, size, its tail and a "
+                         "seeded sample of its bytes) and the timed region's counters -- as DIR/<name>.npy (float32 / float64, < 64 MB).  "
+                         "Such a run writes its archive to a file: its times are not the headline's")
     ap.add_argument("--cpu-baseline-mbp", type=float, default=300.0, help="size of the CPU baseline sample (Mbp per genome)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline (implies --full)")
     ap.add_argument("--positional-splitters", action="store_true",
                     help="skip determine_splitters: take the k-mer at every segment_size-th position (valid for an i.i.d. reference)")
     ap.add_argument("--pack-cardinality", type=int, default=0, metavar="B",
@@ -81,7 +95,12 @@ def parse():
                     help="CHECKING RUN, not a measurement: every frame the device entropy stage returns (all the packs of this run's Close) is "
                          "compressed again by the host's libzstd 1.4.9 at level 17 and compared byte for byte (AGC_AMD_VERIFY_DEV_FRAMES); "
                          "Close() fails on a difference.  The line's `value` includes that work -- keep the log, not the number")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.no_cpu_baseline:
+        args.full = True
+    if args.dump_outputs and (args.config != "c2" or args.from_fasta):
+        ap.error("--dump-outputs belongs to the headline workload (--config c2, HBM-resident samples)")
+    return args
 
 
 def cgroup_cpu_stat():
@@ -461,6 +480,36 @@ def _sha256_file(path):
     return h.hexdigest()
 
 
+# counters of the timed region that depend on the inputs and the code only (not on timing or on the host / device split of the
+# entropy stage): what the steps and Close() produced
+DUMP_COUNTERS = ("bases", "segments", "lz_encoded", "delta_bytes", "middle_tried", "middle_split", "one_splitter", "new_groups",
+                 "zstd_in", "zstd_out")
+DUMP_SAMPLE_BYTES = 8 << 20  # archive bytes sampled at seeded positions (float32: 32 MB)
+DUMP_TAIL_BYTES = 4 << 20    # the archive's last bytes, whole (float32: 16 MB): Close()'s packs of the timed samples + the collection
+
+
+def dump_outputs(out_dir, archive_path, stats):
+    """What a caller of the timed path receives is the archive.  Written as DIR/<name>.npy, every byte value exact in float32:
+    archive_sha256 (32 bytes), archive_size, archive_tail, archive_sample (the bytes at DUMP_SAMPLE_BYTES positions drawn with a
+    fixed seed over the archive's size, ascending) + counters (DUMP_COUNTERS of the timed region, float64, in that order)."""
+    import hashlib
+    os.makedirs(out_dir, exist_ok=True)
+    size = os.path.getsize(archive_path)
+    arc = np.memmap(archive_path, dtype=np.uint8, mode="r") if size else np.zeros(0, np.uint8)
+    h = hashlib.sha256()
+    for b in range(0, size, 1 << 26):
+        h.update(arc[b:b + (1 << 26)])
+    pos = np.sort(np.random.default_rng(20240531).integers(0, size, min(size, DUMP_SAMPLE_BYTES))) if size else np.zeros(0, np.int64)
+    out = {"archive_sha256": np.frombuffer(h.digest(), np.uint8).astype(np.float64),
+           "archive_size": np.array([size], np.float64),
+           "archive_tail": np.asarray(arc[max(0, size - DUMP_TAIL_BYTES):], np.float32),
+           "archive_sample": np.asarray(arc[pos], np.float32),
+           "counters": np.array([stats[k_] for k_ in DUMP_COUNTERS], np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    del arc
+
+
 def main():
     if "--verify-entropy" in sys.argv:
         os.environ["AGC_AMD_VERIFY_DEV_FRAMES"] = "1"
@@ -513,6 +562,11 @@ def main():
     archive_path = os.environ.get("AGC_BENCH_ARCHIVE", "") if rank == 0 or not single else ""
     if archive_path and world > 1 and not single:
         archive_path += f".{rank}"
+    # (--dump-outputs: rank 0's archive is written into DIR for the dump, read after Close() and removed again)
+    dump_tmp = ""
+    if args.dump_outputs and rank == 0 and not archive_path:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        archive_path = dump_tmp = os.path.join(args.dump_outputs, "archive.agc.tmp")
     cmp_.create(archive_path, pack_card, K, None, SEG, MML, n_threads=threads)
     # reference preprocessing (once per archive, not timed): the reference's determine_splitters on the GPU
     t_spl0 = time.perf_counter()
@@ -577,12 +631,15 @@ def main():
     # --prepacked: packed before the timer starts, as in round 4.
     samples = [None] * n_steps      # (Packed, backing tensors) once packed
     sample_off = [off] * n_steps    # the contigs' symbol offsets as the pack returns them
-    fasta = []                      # per sample: (raw bytes in HBM, n_raw, raw_begin, raw_end, (words, index, esc))
+    fasta = []                      # per distinct sample: (raw bytes in HBM, n_raw, raw_begin, raw_end, (words, index, esc))
+    # (--prepacked keeps every sample packed, 0.7 GiB each, as it always did; the FASTA-byte inputs share MAX_SAMPLE_SLOTS slots)
+    n_slots = n_steps if args.prepacked else min(n_steps, MAX_SAMPLE_SLOTS)
+    slot_subst = []                 # per slot: the positions where its current sample differs from the reference (int64, device)
     pack_pending = {}
     pack_ms_each = []
     AS_BUILT_BPS["pack"] = 2.0 * (1.0 + 1.0 / args.fasta_width) + 0.25  # (both passes read the bytes)
     PACKED_BPS["pack"] = 1.0 + 1.0 / args.fasta_width + 0.25           # (one read + the words: the algorithmic figure)
-    for s in range(n_steps):
+    for s in range(n_slots):
         codes = synth_dev.make_sample(ref, tot, args.div, shard.sample_seed(1000, s, rank, world), dev)
         if args.prepacked:
             samples[s] = hctx.pack_dev(codes, tot)
@@ -592,25 +649,73 @@ def main():
                     torch.empty(int(hctx.L.agc_hip_packed_index_bytes(tot)) // 4 + 1, dtype=torch.int32, device=dev),
                     torch.empty(64 * 1024, dtype=torch.uint8, device=dev))
             fasta.append((raw, n_raw, rb, re_, bufs))
+            if n_steps > n_slots:
+                slot_subst.append(torch.cat([(codes[b:min(b + (1 << 28), tot)] != ref[b:min(b + (1 << 28), tot)]).nonzero()[:, 0] + b
+                                             for b in range(0, tot, 1 << 28)]))
         del codes
     torch.cuda.synchronize()
+    gen_stream = torch.cuda.Stream(device=dev)  # (the refills: a stream of their own, not ordered behind the library's)
+    off_t = torch.tensor(np.asarray(off, np.int64), device=dev)
+    rb_t = torch.tensor(np.asarray(fasta[0][2], np.int64), device=dev) if fasta else None  # (the same layout for every sample)
+    acgt = torch.tensor(list(b"ACGT"), dtype=torch.uint8, device=dev)
+
+    refill = {}                     # slot -> (the step whose sample it is being refilled with, event recorded after the refill)
+    refill_wait = [0.0]             # host seconds a conversion's queueing waited for its slot's refill (the refills run ahead)
+
+    def resample_slot(s):
+        """queues, on gen_stream, step s's sample into slot s % n_slots: the reference with substitutions at rate --div drawn from
+        step s's seed (a Binomial count of positions, each base replaced by one of the other three, as synth_dev.make_sample does),
+        written over the slot's FASTA bytes after the previous sample's substitutions are put back to the reference's letters.  A few
+        million scattered bytes, queued as soon as the slot's previous sample has been converted (its bytes are not read again):
+        they run on the GPU beside the steps in between, and nothing waits for them on the host (no size-dependent call)."""
+        j = s % n_slots
+        raw = fasta[j][0]
+        seed = shard.sample_seed(1000, s, rank, world)
+
+        def at(p):  # symbol position -> its byte in the FASTA file (header lines, --fasta-width letters per line)
+            c = torch.searchsorted(off_t, p, right=True) - 1
+            i = p - off_t[c]
+            return rb_t[c] + i + i // args.fasta_width
+        with torch.cuda.stream(gen_stream):
+            old = slot_subst[j]
+            raw[at(old)] = acgt[ref[old].long()]
+            g = torch.Generator(device=dev)
+            g.manual_seed(seed)
+            new = torch.randint(0, tot, (int(np.random.default_rng(seed).binomial(tot, args.div)),), generator=g, device=dev)
+            # the new base: one of the other three, chosen by a hash of (position, seed) -- a position drawn twice gets the same
+            # byte both times, so the scattered writes are the same whatever order they land in
+            h = ((new ^ seed) * 6364136223846793005 + 1442695040888963407) >> 33
+            raw[at(new)] = acgt[((ref[new].long() + 1 + (h & 0x7FFFFFFF) % 3) & 3)]
+            slot_subst[j] = new
+            ev = torch.cuda.Event()
+            ev.record(gen_stream)
+        refill[j] = (s, ev)
 
     def start_pack(s):
         # announced to the compressor, which queues the conversion where the sample call in progress leaves the GPU room for it
         # (behind its classification kernels, beside the registration's host work and the announced scan) -- or at once, in
         # packed_sample(), when no sample call comes in between (the first two samples of the warm-up and of the timed region)
         if samples[s] is None and s not in pack_pending:
-            raw, n_raw, rb, re_, bufs = fasta[s]
+            if s >= n_slots:
+                if refill.get(s % n_slots, (None,))[0] != s:
+                    resample_slot(s)
+                t_ = time.perf_counter()
+                refill[s % n_slots][1].synchronize()  # (queued n_slots - 2 steps ago: long done)
+                refill_wait[0] += time.perf_counter() - t_
+            raw, n_raw, rb, re_, bufs = fasta[s % n_slots]
             pack_pending[s] = cmp_.set_next_fasta_dev(raw, n_raw, rb, re_, bufs)
 
     def packed_sample(s):
         if samples[s] is None:
             start_pack(s)
             pk, keep, o_ = cmp_.finish_fasta_dev(pack_pending.pop(s))
-            pack_ms_each.append(round(hctx.timing_get()["pack"][0], 3))  # (cumulative while timing is on: differences = each pack)
+            if args.full:
+                pack_ms_each.append(round(hctx.timing_get()["pack"][0], 3))  # (cumulative while timing is on: differences = each pack)
             if not np.array_equal(o_, np.asarray(off, np.uint64)):
                 raise SystemExit(f"bench.py: the pack of sample {s} returned other contig offsets than the generator's")
             samples[s], sample_off[s] = (pk, keep), o_
+            if not args.prepacked and s + n_slots < n_steps:
+                resample_slot(s + n_slots)  # (this sample's FASTA bytes are converted: its slot takes the sample of step s + n_slots)
         return samples[s]
 
     def barrier():
@@ -623,7 +728,8 @@ def main():
         add_step(s, "w")
     cmp_.drain()
     st0 = cmp_.stats()
-    cmp_.hip_timing(True)  # HIP events on the library's stream around every kernel of the timed region
+    if args.full:
+        cmp_.hip_timing(True)  # HIP events on the library's stream around every kernel of the timed region
     barrier()
     sec0 = dict(dc.seconds) if dc is not None else None
     bytes0 = (dc.bytes_broadcast, dc.bytes_p2p, dc.n_records) if dc is not None else None
@@ -648,7 +754,7 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     cg2 = cgroup_cpu_stat()
-    tm = cmp_.hip_timing_get()
+    tm = cmp_.hip_timing_get() if args.full else {}
     st1 = cmp_.stats()
     stats = {k_: st1[k_] - st0[k_] for k_ in st1}
     if world > 1:
@@ -679,7 +785,7 @@ def main():
         tab = pmc_table()
         kern = {}
         for name in ("pack", "scan", "encode", "estimate", "costvec", "filter"):
-            ms_, n_ = tm[name]
+            ms_, n_ = tm.get(name, (0.0, 0))  # (no rows without --full: the timed region runs without HIP events)
             if not n_:
                 continue
             ms_step = ms_ / max(args.steps, 1)
@@ -736,7 +842,13 @@ def main():
                                        "scan is queued ahead); the entropy stage (zstd 17 of full delta packs: GPU kernel + host "
                                        "pool; 13/19 of new references: host pool) runs on a background "
                                        "thread beside the steps; after the last step: Close() = the same for every open pack + archive "
-                                       "metadata, and the wait for it all.  Inputs resident in HBM; archive bytes produced, not written to disk.",
+                                       "metadata, and the wait for it all.  Inputs resident in HBM; "
+                                       + ("archive written to a file (a checking or --dump-outputs run, not the headline's path)." if archive_path else
+                                          "archive bytes produced, not written to disk."),
+                       "dump_run": bool(args.dump_outputs),
+                       "sample_slots": n_slots,
+                       "resampled_samples": max(0, n_steps - n_slots),  # (samples written over a reused slot while the run goes on)
+                       "resample_wait_ms": round(refill_wait[0] * 1e3, 3),  # (host time the steps waited for those refills)
                        "setup_not_timed": f"determine_splitters ({'positional shortcut' if args.positional_splitters else 'GPU: enumerate + radix sort + singletons'}): "
                                           f"{t_spl:.2f} s; reference genome as first sample (mints ~{int(st0['new_groups'])} groups): {t_ref:.2f} s",
                        "steps_only_ms": round(t_steps / max(args.steps, 1) * 1e3, 3),
@@ -748,7 +860,7 @@ def main():
                                        "close": {"cpu_s": round((cg2.get("usage_usec", 0) - cg1.get("usage_usec", 0)) / 1e6, 3),
                                                  "throttled_s": round((cg2.get("throttled_usec", 0) - cg1.get("throttled_usec", 0)) / 1e6, 3),
                                                  "nr_throttled": cg2.get("nr_throttled", 0) - cg1.get("nr_throttled", 0)}} if cg0 else None),
-                       "pack_ms_cumulative_after_each_pack": pack_ms_each[-(args.steps + 2):],
+                       "pack_ms_cumulative_after_each_pack": pack_ms_each[-(args.steps + 2):] if args.full else None,
                        **({"archive_sha256": _sha256_file(archive_path), "archive_bytes": os.path.getsize(archive_path)} if archive_path else {}),
                        "close_ms": round((elapsed - t_steps) * 1e3, 1),
                        "segments_per_step": int(per(stats["segments"])), "lz_encoded_per_step": int(per(stats["lz_encoded"])),
@@ -791,11 +903,17 @@ def main():
                          "kernels": kern,
                          "kernel_ms_per_step_rank0": {n: round(v[0] / max(args.steps, 1), 4) for n, v in tm.items() if v[1]}},
         }
-        if not args.no_cpu_baseline and world == 1:  # reported on rank 0 at N = 1 only
+        if not args.full:
+            del out["roofline"]  # (per-kernel figures: --full)
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported on rank 0 at N = 1 only
             try:
                 out["cpu_baseline"] = cpu_baseline(args, args.cpu_baseline_mbp)
             except Exception as e:  # the baseline is informational; never lose the GPU line
                 out["cpu_baseline"] = {"value": None, "unit": "Gbp/s", "cores": 0, "kind": "port", "sample": f"failed: {e}"}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, archive_path, stats)
+            if dump_tmp:
+                os.remove(dump_tmp)
         print(json.dumps(out), flush=True)
     cmp_.close_handle()  # tear the HIP context down before the interpreter (and any profiler) exits
     if world > 1:
