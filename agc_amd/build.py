@@ -56,7 +56,7 @@ def build(force=False, verbose=False):
 HOST = os.path.join(CSRC, "host")
 HOST_LIB = os.path.join(HERE, "libagc_host.so")
 HOST_BIN = os.path.join(HERE, "bin", "agc_amd")
-HOST_SOURCES = ["compressor.cpp", "compressor_batch.cpp", "compressor_dist.cpp", "compressor_impl.h", "compressor.h", "host_support.h",
+HOST_SOURCES = ["compressor.cpp", "compressor_batch.cpp", "compressor_dist.cpp", "compressor_impl.h", "compressor.h", "host_support.h", "switches.h",
                 "capi_host.cpp", "main.cpp", "reader.cpp", "reader.h", "capi_read.cpp", "archive_read.h"]
 HOST_LIB_SOURCES = ["compressor.cpp", "compressor_batch.cpp", "compressor_dist.cpp", "capi_host.cpp", "reader.cpp"]
 READ_LIB = os.path.join(HERE, "libagc_read.so")

@@ -90,20 +90,8 @@ bool CAGCCompressor::SetReferenceDevice(const uint8_t *d_codes, const uint64_t *
     Impl &I = *p;
     if (!I.created || I.adaptive)
         return false;
-    const uint64_t tot = n_ctg ? ctg_off[n_ctg] - ctg_off[0] : 0;
-    std::vector<uint64_t> spl(std::max<uint64_t>(1024, tot / std::max(1u, I.segment_size) * 2 + 2ull * n_ctg + 16));
-    uint64_t n_spl = 0;
-    for (;;) {
-        int rc = agc_hip_determine_splitters_dev(I.hip, d_codes, ctg_off, n_ctg, I.k, I.segment_size, spl.size(), spl.data(), &n_spl, 0, nullptr, nullptr);
-        if (rc == AGC_HIP_ECAP && n_spl > spl.size()) {
-            spl.resize(n_spl);
-            continue;
-        }
-        if (!I.hip_ok(rc, "determine_splitters"))
-            return false;
-        break;
-    }
-    return SetSplitters(spl.data(), n_spl);
+    std::vector<uint64_t> spl;
+    return I.splitters_of(d_codes, ctg_off, n_ctg, spl, nullptr) && SetSplitters(spl.data(), spl.size());
 }
 
 void StartLap(const char *what) { start_lap(what); }
@@ -148,52 +136,8 @@ bool CAGCCompressor::Create(const std::string &file_name, uint32_t pack_cardinal
         return false;
     }
     start_lap("libzstd opened");
-    if (!I.hip) {
-        int rc = agc_hip_create(&I.hip, I.device);
-        if (rc != AGC_HIP_OK) {
-            I.err("no HIP device: the MI355X path has no CPU fallback (agc_hip_create = " + std::to_string(rc) + ")");
-            return false;
-        }
-    }
-    start_lap("device context (runtime, streams, events)");
-    unsigned nt = std::max(1u, no_threads);
-    I.pool.reset(new ThreadPool(nt));
-    I.zpool.reset(new ThreadPool(nt, 10));
-    I.bpool.reset(new ThreadPool(std::max(1u, std::min(8u, nt / 2))));
-    if (const char *e = getenv("AGC_AMD_ASYNC_BOOK"))
-        I.async_book = atoi(e) != 0;
-    if (const char *e = getenv("AGC_AMD_ASYNC_ENCODE"))
-        I.async_encode = atoi(e) != 0;
-    if (const char *e = getenv("AGC_AMD_EARLY_COLLECT"))
-        I.early_collect = atoi(e) != 0;
-    if (const char *e = getenv("AGC_AMD_REF_STORE_ASYNC"))
-        I.ref_store_async = atoi(e) != 0;
-    I.enc_alt.ctx = I.enc_alt2.ctx = I.hip;
-    for (unsigned i = 0; i < nt; ++i)
-        I.zctx.emplace_back(new ZstdCtx(&I.zstd));
-    I.sync_entropy = getenv("AGC_AMD_SYNC_ENTROPY") != nullptr;
-    if (const char *e = getenv("AGC_AMD_ENTROPY_STREAM"))
-        I.entropy_stream = atoi(e) != 0;
-    I.enc_buf.ctx = I.enc_buf2.ctx = I.dist_body_buf.ctx = I.dist_record_buf.ctx = I.hip;
-    if (const char *e = getenv("AGC_AMD_PAR_MIN"))
-        I.par_min = (size_t)std::max(1LL, atoll(e));
-    if (const char *e = getenv("AGC_AMD_ENCODE_OVERLAP"))
-        I.overlap_mode = !strcmp(e, "early") || !strcmp(e, "1") ? 1 : !strcmp(e, "late") || !strcmp(e, "2") ? 2 : 0;
-    I.choose_entropy_stage();
-    if (const char *e = getenv("AGC_AMD_DEV_SEGMENTS"))
-        I.dev_segments = atoi(e) != 0;
-    if (const char *e = getenv("AGC_AMD_DEV_ENCODE_MIN"))
-        I.dev_encode_min = (uint32_t)std::max(0, atoi(e));
-    if (const char *e = getenv("AGC_AMD_PRE_LAUNCH_ENCODE"))
-        I.pre_launch_encode = atoi(e) != 0;
-    if (const char *e = getenv("AGC_AMD_PLACE_AHEAD"))
-        I.place_ahead = atoi(e);
-    if (const char *e = getenv("AGC_AMD_SPEC_FILL_AHEAD"))
-        I.spec_fill_ahead = atoi(e);
-    if (!PkMap::hash_agrees()) {
-        I.err("internal: the host's and the device library's group hash differ");
+    if (!I.open_session(no_threads))
         return false;
-    }
     I.created = true;
     start_lap("pools, zstd contexts");
 
@@ -203,21 +147,11 @@ bool CAGCCompressor::Create(const std::string &file_name, uint32_t pack_cardinal
         // samples' (AddSampleFiles)
         std::vector<bytes_t> ref;
         {
-            std::vector<std::string> ids;
-            static const uint64_t map_min = getenv("AGC_AMD_MAP_MIN") ? strtoull(getenv("AGC_AMD_MAP_MIN"), nullptr, 10) : (64ull << 20);
-            if (!FastaReader::read_all_mapped(reference_file_name, ids, ref, std::max(1u, std::min(8u, nt)), map_min)) {
-                FastaReader fr;
-                if (!fr.open(reference_file_name)) {
-                    I.err("Cannot open file: " + reference_file_name);
-                    I.created = false;
-                    return false;
-                }
-                std::string id;
-                bytes_t c;
-                while (fr.read_contig_raw(id, c)) {
-                    ref.emplace_back(std::move(c));
-                    c.clear();
-                }
+            std::vector<std::string> ids; // (not kept)
+            if (!FastaReader::read_file(reference_file_name, ids, ref, std::max(1u, std::min(8u, no_threads)), I.sw.map_min)) {
+                I.err("Cannot open file: " + reference_file_name);
+                I.created = false;
+                return false;
             }
         }
         uint64_t tot_raw = 0;
@@ -243,26 +177,11 @@ bool CAGCCompressor::Create(const std::string &file_name, uint32_t pack_cardinal
             off[i + 1] = off[i] + n_codes;
             bytes_t().swap(ref[i]); // (the host copy is not needed any more)
         }
-        const uint64_t tot = off[ref.size()];
-        std::vector<uint64_t> spl(std::max<uint64_t>(1024, tot / std::max(1u, I.segment_size) * 2 + 2 * ref.size() + 16));
-        std::vector<uint64_t> sorted_kmers(I.adaptive ? tot : 0);
-        uint64_t n_spl = 0, n_sorted = 0;
-        for (;;) {
-            int rc = agc_hip_determine_splitters_dev(I.hip, d_ref, off.data(), (uint32_t)ref.size(), I.k, I.segment_size, spl.size(), spl.data(),
-                                                     &n_spl, sorted_kmers.size(), I.adaptive ? sorted_kmers.data() : nullptr,
-                                                     I.adaptive ? &n_sorted : nullptr);
-            if (rc == AGC_HIP_ECAP && n_spl > spl.size()) {
-                spl.resize(n_spl);
-                continue;
-            }
-            if (!I.hip_ok(rc, "determine_splitters"))
-                return false;
-            break;
-        }
-        spl.resize(n_spl);
+        std::vector<uint64_t> spl, sorted_kmers;
+        if (!I.splitters_of(d_ref, off.data(), (uint32_t)ref.size(), spl, I.adaptive ? &sorted_kmers : nullptr))
+            return false;
         if (I.adaptive) {
             // v_candidate_kmers (singletons) and v_duplicated_kmers (agc_compressor.cpp:493-497)
-            sorted_kmers.resize(n_sorted);
             split_singletons(sorted_kmers, &I.ref_duplicates);
             I.ref_singletons.swap(sorted_kmers);
         }
@@ -351,51 +270,8 @@ bool CAGCCompressor::Append(const std::string &in_archive_name, const std::strin
     I.verbosity = verbosity;
     I.appending = true;
 
-    if (!I.hip) {
-        int rc = agc_hip_create(&I.hip, I.device);
-        if (rc != AGC_HIP_OK) {
-            I.err("no HIP device: the MI355X path has no CPU fallback (agc_hip_create = " + std::to_string(rc) + ")");
-            return false;
-        }
-    }
-    unsigned nt = std::max(1u, no_threads);
-    I.pool.reset(new ThreadPool(nt));
-    I.zpool.reset(new ThreadPool(nt, 10));
-    I.bpool.reset(new ThreadPool(std::max(1u, std::min(8u, nt / 2))));
-    if (const char *e = getenv("AGC_AMD_ASYNC_BOOK"))
-        I.async_book = atoi(e) != 0;
-    if (const char *e = getenv("AGC_AMD_ASYNC_ENCODE"))
-        I.async_encode = atoi(e) != 0;
-    if (const char *e = getenv("AGC_AMD_EARLY_COLLECT"))
-        I.early_collect = atoi(e) != 0;
-    if (const char *e = getenv("AGC_AMD_REF_STORE_ASYNC"))
-        I.ref_store_async = atoi(e) != 0;
-    I.enc_alt.ctx = I.enc_alt2.ctx = I.hip;
-    for (unsigned i = 0; i < nt; ++i)
-        I.zctx.emplace_back(new ZstdCtx(&I.zstd));
-    I.sync_entropy = getenv("AGC_AMD_SYNC_ENTROPY") != nullptr;
-    if (const char *e = getenv("AGC_AMD_ENTROPY_STREAM"))
-        I.entropy_stream = atoi(e) != 0;
-    I.enc_buf.ctx = I.enc_buf2.ctx = I.dist_body_buf.ctx = I.dist_record_buf.ctx = I.hip;
-    if (const char *e = getenv("AGC_AMD_PAR_MIN"))
-        I.par_min = (size_t)std::max(1LL, atoll(e));
-    if (const char *e = getenv("AGC_AMD_ENCODE_OVERLAP"))
-        I.overlap_mode = !strcmp(e, "early") || !strcmp(e, "1") ? 1 : !strcmp(e, "late") || !strcmp(e, "2") ? 2 : 0;
-    I.choose_entropy_stage();
-    if (const char *e = getenv("AGC_AMD_DEV_SEGMENTS"))
-        I.dev_segments = atoi(e) != 0;
-    if (const char *e = getenv("AGC_AMD_DEV_ENCODE_MIN"))
-        I.dev_encode_min = (uint32_t)std::max(0, atoi(e));
-    if (const char *e = getenv("AGC_AMD_PRE_LAUNCH_ENCODE"))
-        I.pre_launch_encode = atoi(e) != 0;
-    if (const char *e = getenv("AGC_AMD_PLACE_AHEAD"))
-        I.place_ahead = atoi(e);
-    if (const char *e = getenv("AGC_AMD_SPEC_FILL_AHEAD"))
-        I.spec_fill_ahead = atoi(e);
-    if (!PkMap::hash_agrees()) {
-        I.err("internal: the host's and the device library's group hash differ");
+    if (!I.open_session(no_threads))
         return false;
-    }
 
     if (!I.ar.open(out_archive_name)) {
         I.err("Cannot create archive " + out_archive_name);
@@ -449,21 +325,9 @@ bool CAGCCompressor::Append(const std::string &in_archive_name, const std::strin
                 return false;
             off[i + 1] = off[i] + ref[i].size();
         }
-        std::vector<uint64_t> spl(std::max<uint64_t>(1024, tot / std::max(1u, I.segment_size) * 2 + 2 * ref.size() + 16));
-        std::vector<uint64_t> sorted_kmers(tot);
-        uint64_t n_spl = 0, n_sorted = 0;
-        for (;;) {
-            int rc = agc_hip_determine_splitters_dev(I.hip, d_ref, off.data(), (uint32_t)ref.size(), I.k, I.segment_size, spl.size(), spl.data(),
-                                                     &n_spl, sorted_kmers.size(), sorted_kmers.data(), &n_sorted);
-            if (rc == AGC_HIP_ECAP && n_spl > spl.size()) {
-                spl.resize(n_spl);
-                continue;
-            }
-            if (!I.hip_ok(rc, "determine_splitters"))
-                return false;
-            break;
-        }
-        sorted_kmers.resize(n_sorted);
+        std::vector<uint64_t> spl, sorted_kmers;
+        if (!I.splitters_of(d_ref, off.data(), (uint32_t)ref.size(), spl, &sorted_kmers))
+            return false;
         split_singletons(sorted_kmers, &I.ref_duplicates);
         I.ref_singletons.swap(sorted_kmers);
     }
@@ -598,6 +462,62 @@ bool CAGCCompressor::Impl::unpack_group(uint32_t gid)
     return true;
 }
 
+// What Create and Append share of a session's start: the device context, the pools with a zstd context per thread, the context of
+// the pinned buffers, the switches and the entropy stage chosen from them.  false: the message is out.
+bool CAGCCompressor::Impl::open_session(unsigned no_threads)
+{
+    if (!hip) {
+        int rc = agc_hip_create(&hip, device);
+        if (rc != AGC_HIP_OK) {
+            err("no HIP device: the MI355X path has no CPU fallback (agc_hip_create = " + std::to_string(rc) + ")");
+            return false;
+        }
+    }
+    if (!appending)
+        start_lap("device context (runtime, streams, events)");
+    const unsigned nt = std::max(1u, no_threads);
+    pool.reset(new ThreadPool(nt));
+    zpool.reset(new ThreadPool(nt, 10));
+    bpool.reset(new ThreadPool(std::max(1u, std::min(8u, nt / 2))));
+    for (unsigned i = 0; i < nt; ++i)
+        zctx.emplace_back(new ZstdCtx(&zstd));
+    enc_alt.ctx = enc_alt2.ctx = enc_buf.ctx = enc_buf2.ctx = dist_body_buf.ctx = dist_record_buf.ctx = hip;
+    sw = Switches::read();
+    choose_entropy_stage();
+    if (!PkMap::hash_agrees()) {
+        err("internal: the host's and the device library's group hash differ");
+        return false;
+    }
+    return true;
+}
+
+// determine_splitters for contigs that lie in HBM back to back (off: n_ctg + 1 offsets): the splitters into spl and, for the
+// adaptive mode, every k-mer of the contigs, sorted, into *sorted_kmers.  The splitters' number is guessed from the length and
+// the call repeated with room for all of them when the guess was short.
+bool CAGCCompressor::Impl::splitters_of(const uint8_t *d_codes, const uint64_t *off, uint32_t n_ctg, std::vector<uint64_t> &spl, std::vector<uint64_t> *sorted_kmers)
+{
+    const uint64_t tot = n_ctg ? off[n_ctg] - off[0] : 0;
+    spl.resize(std::max<uint64_t>(1024, tot / std::max(1u, segment_size) * 2 + 2ull * n_ctg + 16));
+    if (sorted_kmers)
+        sorted_kmers->resize(tot);
+    uint64_t n_spl = 0, n_sorted = 0;
+    for (;;) {
+        int rc = agc_hip_determine_splitters_dev(hip, d_codes, off, n_ctg, k, segment_size, spl.size(), spl.data(), &n_spl, sorted_kmers ? sorted_kmers->size() : 0,
+                                                 sorted_kmers ? sorted_kmers->data() : nullptr, sorted_kmers ? &n_sorted : nullptr);
+        if (rc == AGC_HIP_ECAP && n_spl > spl.size()) {
+            spl.resize(n_spl);
+            continue;
+        }
+        if (!hip_ok(rc, "determine_splitters"))
+            return false;
+        break;
+    }
+    spl.resize(n_spl);
+    if (sorted_kmers)
+        sorted_kmers->resize(n_sorted);
+    return true;
+}
+
 // Delta packs go to the GPU entropy stage when its frames are the ones the host's libzstd would write (the device encoder
 // restates libzstd 1.4.9; 1.4.8 writes the same level-17 frames): references and metadata stay on libzstd, and one archive
 // must not mix encoder versions.  AGC_AMD_HOST_ZSTD=1 keeps everything on the host, AGC_AMD_GPU_ZSTD=force overrides the check.
@@ -605,17 +525,12 @@ void CAGCCompressor::Impl::choose_entropy_stage()
 {
     const std::string v = zstd.versionString ? zstd.versionString() : "";
     gpu_zstd = (v == "1.4.9" || v == "1.4.8");
-    if (const char *e = getenv("AGC_AMD_GPU_ZSTD"))
-        if (std::string(e) == "force")
-            gpu_zstd = true;
-    if (getenv("AGC_AMD_HOST_ZSTD"))
+    if (sw.gpu_zstd_force)
+        gpu_zstd = true;
+    if (sw.host_zstd)
         gpu_zstd = false;
-    if (const char *e = getenv("AGC_AMD_GPU_ZSTD_SHARE"))
-        gpu_zstd_share = std::min(1.0, std::max(0.0, atof(e)));
-    if (const char *e = getenv("AGC_AMD_GPU_ZSTD_MIN"))
-        gpu_zstd_min = (uint32_t)std::max(1, atoi(e));
-    if (const char *e = getenv("AGC_AMD_GPU_ZSTD_REFS"))
-        gpu_zstd_refs_min = (uint32_t)std::max(0, atoi(e));
+    if (sw.share_fixed)
+        gpu_zstd_share = sw.gpu_zstd_share;
     if (verbosity > 0)
         std::cerr << "entropy stage: delta packs on " << (gpu_zstd ? "the GPU (zstd 1.4.9 frames)" : "host libzstd") << ", libzstd " << v << std::endl;
 }
@@ -932,15 +847,14 @@ bool CAGCCompressor::AddSampleFiles(const std::vector<std::pair<std::string, std
     uint64_t pending_bytes = 0;
     const uint64_t WINDOW_BYTES = 64ull << 20;
     // (AGC_AMD_WINDOW_MAX: tests pin the window, e.g. to 1 = every registration on its own, bookkeeping beside the next one)
-    static const uint32_t window_cap = getenv("AGC_AMD_WINDOW_MAX") ? (uint32_t)std::max(1, atoi(getenv("AGC_AMD_WINDOW_MAX"))) : 256u;
     // (adaptive mode: new splitters change later scans -- a window is cut at the registration that brings some, stage_scan_dev;
     // without the device's segments there is no such cut and no speculation)
-    const uint32_t WINDOW_MAX = I.adaptive && !I.adaptive_windows() ? 1u : window_cap;
+    const uint32_t WINDOW_MAX = I.adaptive && !I.adaptive_windows() ? 1u : I.sw.window_max;
     uint32_t window = 1; // grows while whole windows commit, shrinks to what did commit otherwise
     // (adaptive mode mines new splitters from host copies of the codes, k < 16 scans one byte per symbol: the earlier path.
     // AGC_AMD_FASTA_PACK=0 switches the one-pass conversion off, AGC_AMD_FASTA_PACK_MIN=<bytes> moves its threshold)
-    const bool fasta_ok = !I.adaptive && I.k >= 16 && !(getenv("AGC_AMD_FASTA_PACK") && atoi(getenv("AGC_AMD_FASTA_PACK")) == 0);
-    const uint64_t FASTA_PACK_MIN = getenv("AGC_AMD_FASTA_PACK_MIN") ? strtoull(getenv("AGC_AMD_FASTA_PACK_MIN"), nullptr, 10) : (1ull << 20);
+    const bool fasta_ok = !I.adaptive && I.k >= 16 && I.sw.fasta_pack;
+    const uint64_t FASTA_PACK_MIN = I.sw.fasta_pack_min;
 
     auto run_window = [&]() -> bool {
         // batch = the first `window` pending registrations (at least one)
@@ -1073,7 +987,7 @@ bool CAGCCompressor::AddSampleFiles(const std::vector<std::pair<std::string, std
     const unsigned read_threads = std::max(1u, std::min(8u, no_threads / 2));
     // (a file of FASTA_PACK_MIN bytes or more keeps EVERY contig as it was read -- the small scaffolds of an assembly beside its
     // chromosomes -- so that its window qualifies for the one-pass conversion; smaller files: per contig, as before)
-    auto read_file = [GPU_A1_MIN, read_threads, fasta_ok, FASTA_PACK_MIN](std::string path) {
+    auto read_file = [GPU_A1_MIN, read_threads, fasta_ok, FASTA_PACK_MIN, map_min = I.sw.map_min](std::string path) {
         FileData fd;
         auto settle = [&]() {
             uint64_t total = 0;
@@ -1087,25 +1001,10 @@ bool CAGCCompressor::AddSampleFiles(const std::vector<std::pair<std::string, std
                     preprocess_raw_contig(fd.contigs[i]);
             }
         };
-        // a big plain file: mapped, cut and copied out by a few threads
-        static const uint64_t map_min = getenv("AGC_AMD_MAP_MIN") ? strtoull(getenv("AGC_AMD_MAP_MIN"), nullptr, 10) : (64ull << 20);
-        if (FastaReader::read_all_mapped(path, fd.ids, fd.contigs, read_threads, map_min)) {
-            fd.opened = true;
+        // (a big plain file: mapped, cut and copied out by a few threads)
+        fd.opened = FastaReader::read_file(path, fd.ids, fd.contigs, read_threads, map_min);
+        if (fd.opened)
             settle();
-            return fd;
-        }
-        FastaReader fr;
-        if (!fr.open(path))
-            return fd;
-        fd.opened = true;
-        std::string id;
-        bytes_t contig;
-        while (fr.read_contig_raw(id, contig)) {
-            fd.ids.emplace_back(id);
-            fd.contigs.emplace_back(std::move(contig));
-            contig.clear();
-        }
-        settle();
         return fd;
     };
     auto file_bytes = [](const std::string &path) -> uint64_t {
@@ -1259,7 +1158,7 @@ bool CAGCCompressor::CloseCollectPacks(const uint8_t **src, const uint64_t **off
     I.deferred_bytes = 0;
     const size_t n_kept = I.close_jobs.size();
     I.build_close_jobs(I.close_jobs);
-    if (getenv("AGC_AMD_LAPS"))
+    if (laps_on())
         std::cerr << "  CloseCollectPacks: " << n_kept << " packs kept from the run + " << I.close_jobs.size() - n_kept << " open ones\n";
     I.close_dev_jobs.clear();
     const uint32_t dev_max = agc_hip_zstd17_max_input();
@@ -1466,7 +1365,7 @@ bool CAGCCompressor::Close(uint32_t no_threads)
     std::future<void> open_batch;
     if (!I.close_collected)
         open_batch = std::async(std::launch::async, [&I] { I.store_open_batch(false); });
-    const bool laps = getenv("AGC_AMD_LAPS") != nullptr;
+    const bool laps = laps_on();
     double lt = now();
     auto LAP = [&](const char *what) {
         if (laps)
@@ -1540,7 +1439,7 @@ bool CAGCCompressor::Close(uint32_t no_threads)
     // written so that archives stay byte-identical to its output; AGC_AMD_PRODUCER_TAG=1 tags the
     // producer honestly instead (archives then differ in this one stream).
     std::map<std::string, std::string> info;
-    const bool tag = getenv("AGC_AMD_PRODUCER_TAG") != nullptr;
+    const bool tag = I.sw.producer_tag;
     info["producer"] = tag ? "agc_amd" : "agc";
     info["producer_version_major"] = "3";
     info["producer_version_minor"] = "2";

@@ -72,7 +72,7 @@ void CAGCCompressor::Impl::z_main()
             }
             z_busy = true;
         }
-        if (entropy_stream && !heavy_steps.load() && host_only_batch(batch)) {
+        if (sw.entropy_stream && !heavy_steps.load() && host_only_batch(batch)) {
             run_host_stream(std::move(batch)); // (publishes every part as it is finished)
             batch.clear();
         } else {
@@ -95,8 +95,8 @@ void CAGCCompressor::Impl::z_main()
     }
 }
 
-// A batch run_jobs_round would hand to the host pool whole: no device entropy stage, or fewer device-size jobs than a launch is
-// worth (the rule of run_jobs_round: dev_jobs.size() < gpu_zstd_min).
+// A batch plan_entropy_round would hand to the host pool whole: no device entropy stage, or fewer device-size jobs than a launch is
+// worth (its rule: dev_jobs.size() < sw.gpu_zstd_min).
 bool CAGCCompressor::Impl::host_only_batch(const std::vector<ZJob> &jobs) const
 {
     if (!gpu_zstd)
@@ -107,8 +107,8 @@ bool CAGCCompressor::Impl::host_only_batch(const std::vector<ZJob> &jobs) const
         n_refs += j.kind == 0 && !j.data.empty() && j.data.size() <= 65536;
         n_packs += j.kind == 1 && !j.data.empty() && j.data.size() <= dev_max;
     }
-    const bool refs_too = gpu_zstd_refs_min && n_refs >= gpu_zstd_refs_min;
-    return n_packs + (refs_too ? n_refs : 0) < gpu_zstd_min;
+    const bool refs_too = sw.gpu_zstd_refs_min && n_refs >= sw.gpu_zstd_refs_min;
+    return n_packs + (refs_too ? n_refs : 0) < sw.gpu_zstd_min;
 }
 
 // add_to_archive / add_to_archive_tuples / store_in_archive(ref) on the host (segment.h:172-255): one job, libzstd
@@ -351,8 +351,7 @@ void CAGCCompressor::Impl::book_main()
                 }
             }
             lane2_release(0);
-            static const bool early_laps = getenv("AGC_AMD_LAPS") != nullptr;
-            if (early_laps)
+            if (laps_on())
                 std::cerr << "    book task (early): lane 0 collected in " << (now() - t0) * 1e3 << " ms\n";
             t.reset();
             {
@@ -396,8 +395,7 @@ void CAGCCompressor::Impl::book_main()
         const double t_c3 = now();
         book_on_thread = false;
         t.reset();
-        static const bool book_laps = getenv("AGC_AMD_LAPS") != nullptr;
-        if (book_laps) {
+        if (laps_on()) {
             char line[256];
             snprintf(line, sizeof line, "    book task: collect lane 0 %.3f ms, lane 1 %.3f ms, reference store awaited %.3f ms, books %.3f ms, task freed %.3f ms\n",
                      (t_c0 - t0) * 1e3, (t_c1 - t_c0) * 1e3, (t_c2 - t_c1) * 1e3, (t_c3 - t_c2) * 1e3, (now() - t_c3) * 1e3);
@@ -469,31 +467,31 @@ void CAGCCompressor::Impl::lane2_release(int lane)
     book_idle_cv.notify_all();
 }
 
-void CAGCCompressor::Impl::run_jobs_round(std::vector<ZJob> &jobs)
+// A finished frame becomes the job's part: the frame with its marker byte behind it, or the job's own bytes when the frame is not
+// shorter than they are; what was staged for the device is released.
+void CAGCCompressor::Impl::frame_to_job(ZJob &j, const uint8_t *frame, uint32_t n)
 {
-    double t0 = now();
-    static const bool laps = getenv("AGC_AMD_LAPS") != nullptr;
-    double lt = t0;
-    auto LAP = [&](const char *what) {
-        if (laps && jobs.size() > 0)
-            std::cerr << "    entropy lap " << what << " " << (now() - lt) * 1e3 << " ms\n";
-        lt = now();
-    };
-    auto finish = [](ZJob &j, bytes_t &packed, uint32_t ps, uint8_t marker) {
-        packed[ps] = marker;
-        if (ps + 1u < (uint32_t)j.data.size()) {
-            packed.resize((size_t)ps + 1);
-            j.out = std::move(packed);
-            j.meta = j.data.size();
-        } else {
-            j.out = j.data;
-            j.meta = 0;
-        }
-    };
-    // which jobs the device takes
-    std::vector<uint32_t> dev_jobs, host_jobs;
-    const uint32_t dev_max = gpu_zstd ? agc_hip_zstd17_max_input() : 0;
-    const bool ext = close_collected && &jobs == &close_jobs; // frames of the collected packs came in through CloseProvideFrames
+    if (n + 1u < (uint32_t)j.data.size()) {
+        bytes_t packed;
+        packed.reserve((size_t)n + 1);
+        packed.assign(frame, frame + n);
+        packed.push_back(j.kind == 0 ? j.marker : 0);
+        j.out = std::move(packed);
+        j.meta = j.data.size();
+    } else {
+        j.out = j.data;
+        j.meta = 0;
+    }
+    bytes_t().swap(j.staged);
+}
+
+// Which jobs of a round the device takes and which the host pool (longest first).  The policy that decides Close's length: it reads
+// sw, gpu_zstd_share and the device's resident frames, and starts nothing but the tuple staging of the references on the pool.
+CAGCCompressor::Impl::EntropyPlan CAGCCompressor::Impl::plan_entropy_round(std::vector<ZJob> &jobs, bool ext)
+{
+    EntropyPlan plan;
+    std::vector<uint32_t> &dev_jobs = plan.dev_jobs, &host_jobs = plan.host_jobs;
+    const uint32_t dev_max = plan.dev_max = gpu_zstd ? agc_hip_zstd17_max_input() : 0;
     if (ext) {
         std::vector<uint8_t> is_dev(jobs.size(), 0);
         for (uint32_t i : close_dev_jobs)
@@ -508,7 +506,7 @@ void CAGCCompressor::Impl::run_jobs_round(std::vector<ZJob> &jobs)
         // references: to the device when a call brings many of the size a group of lanes codes (the reference sample of a
         // collection with the default segment size); the few long ones -- contigs without a splitter, -s in the hundreds of kb:
         // level 13 above 16 KiB is the one-lane kernel, a launch as long as its longest frame -- stay with the host pool
-        const bool refs_too = gpu_zstd && gpu_zstd_refs_min && n_refs >= gpu_zstd_refs_min;
+        const bool refs_too = gpu_zstd && sw.gpu_zstd_refs_min && n_refs >= sw.gpu_zstd_refs_min;
         if (refs_too)
             zpool->parallel_for(jobs.size(), [&](size_t i, unsigned) {
                 ZJob &j = jobs[i];
@@ -526,7 +524,7 @@ void CAGCCompressor::Impl::run_jobs_round(std::vector<ZJob> &jobs)
             });
         for (uint32_t i = 0; i < jobs.size(); ++i) {
             const ZJob &j = jobs[i];
-            const size_t src_n = j.staged.empty() ? j.data.size() : j.staged.size();
+            const size_t src_n = j.src().size();
             if (gpu_zstd && !j.data.empty() && src_n <= dev_max && (j.kind == 1 || (j.kind == 0 && refs_too && src_n <= 16384)))
                 dev_jobs.push_back(i);
             else
@@ -537,11 +535,11 @@ void CAGCCompressor::Impl::run_jobs_round(std::vector<ZJob> &jobs)
     // byte for the two-pass class <= 16 KiB, ~24 us beyond, a third of that for level 13), while the host pool finishes a small
     // batch in bytes / (threads x ~5 MB/s): the device only takes a batch the pool would need longer for than that.
     bool dev_pays = true;
-    if (!ext && !dev_jobs.empty() && !getenv("AGC_AMD_GPU_ZSTD_SHARE") && gpu_zstd_min > 1) {
+    if (!ext && !dev_jobs.empty() && !sw.share_fixed && sw.gpu_zstd_min > 1) {
         uint64_t tot = 0;
         double longest = 0;
         for (uint32_t i : dev_jobs) {
-            const uint64_t sz = jobs[i].staged.empty() ? jobs[i].data.size() : jobs[i].staged.size();
+            const uint64_t sz = jobs[i].src().size();
             tot += sz;
             double t = (sz <= 16384 ? 48e-6 : 24e-6) * (double)sz;
             if (jobs[i].kind == 0 && jobs[i].level == 13)
@@ -551,7 +549,7 @@ void CAGCCompressor::Impl::run_jobs_round(std::vector<ZJob> &jobs)
         dev_pays = (double)tot / ((double)zpool->size() * 5e6) > longest;
     }
     if (ext) {
-    } else if (dev_jobs.size() < gpu_zstd_min || !dev_pays) { // not worth a launch
+    } else if (dev_jobs.size() < sw.gpu_zstd_min || !dev_pays) { // not worth a launch
         host_jobs.insert(host_jobs.end(), dev_jobs.begin(), dev_jobs.end());
         std::sort(host_jobs.begin(), host_jobs.end());
         dev_jobs.clear();
@@ -559,7 +557,7 @@ void CAGCCompressor::Impl::run_jobs_round(std::vector<ZJob> &jobs)
         // both engines work at the same time: the device keeps the share of the pack bytes that makes them finish together
         // (its measured rate against the host pool's, updated after every call)
         uint64_t total = 0, dev_acc = 0;
-        auto src_size = [&](uint32_t i) -> uint64_t { return jobs[i].staged.empty() ? jobs[i].data.size() : jobs[i].staged.size(); }; // what the encoder reads
+        auto src_size = [&](uint32_t i) -> uint64_t { return jobs[i].src().size(); };
         for (uint32_t i : dev_jobs)
             total += src_size(i);
         // (length of a frame's serial chain: level 17 parses inputs of up to 16 KB twice -- btultra2 -- and larger ones once,
@@ -607,104 +605,181 @@ void CAGCCompressor::Impl::run_jobs_round(std::vector<ZJob> &jobs)
     }
     // host pool: longest jobs first (the tail of the pool is then made of short ones)
     std::stable_sort(host_jobs.begin(), host_jobs.end(), [&](uint32_t a, uint32_t b) { return jobs[a].data.size() > jobs[b].data.size(); });
-    uint64_t host_bytes = 0;
     for (uint32_t i : host_jobs)
         if (jobs[i].kind == 1)
-            host_bytes += jobs[i].data.size();
-    double t_dev = 0, t_host = 0;
-    if (laps && jobs.size() > 0) {
+            plan.host_bytes += jobs[i].data.size();
+    return plan;
+}
+
+// The device's side of a round: its jobs' inputs gathered back to back, then the device call on a thread of its own (dr.done),
+// which also puts the frames back into their jobs.
+void CAGCCompressor::Impl::launch_device_frames(std::vector<ZJob> &jobs, const EntropyPlan &plan, DeviceRound &dr)
+{
+    const std::vector<uint32_t> &dev_jobs = plan.dev_jobs;
+    std::vector<uint64_t> &src_off = dr.src_off, &dst_off = dr.dst_off;
+    const size_t nd = dev_jobs.size();
+    src_off.assign(nd + 1, 0);
+    std::vector<uint8_t> levels(nd);
+    bool any_ref = false;
+    for (size_t t = 0; t < nd; ++t) {
+        const ZJob &j = jobs[dev_jobs[t]];
+        src_off[t + 1] = src_off[t] + j.src().size();
+        levels[t] = j.kind == 0 ? j.level : 17;
+        any_ref = any_ref || j.kind == 0;
+    }
+    const uint64_t cap = src_off[nd] + 32 * nd + 64; // a frame never exceeds its input by more than the headers
+    dst_off.assign(nd + 1, 0);
+    // the packs are gathered by the whole pool (hundreds of MB into fresh pages: a tenth of a second for one thread; the pool's
+    // own jobs wait the 7 ms this takes -- helper threads beside a pool that already uses the whole CPU quota were measured:
+    // the device's side then starts late and ends 57 ms behind the pool), then the device call runs beside the pool's jobs
+    // on a thread of its own, which also puts the frames back into their jobs as soon as the device is done
+    const double tg = now();
+    zsrc_buf.resize(src_off[nd] + src_off[nd] / 8, false); // (headroom: the next call's packs are a little longer)
+    {
+        const size_t n_chunks = std::min<size_t>(nd, (size_t)zpool->size() * 4);
+        zpool->parallel_for(n_chunks, [&](size_t ci, unsigned) {
+            for (size_t t = nd * ci / n_chunks; t < nd * (ci + 1) / n_chunks; ++t) {
+                const bytes_t &srcb = jobs[dev_jobs[t]].src();
+                memcpy(zsrc_buf.data() + src_off[t], srcb.data(), srcb.size());
+            }
+        });
+    }
+    const double t_gather = now() - tg;
+    dr.done = std::async(std::launch::async, [this, &jobs, &dev_jobs, &dr, nd, cap, t_gather, levels, any_ref] {
+        const double td = now() - t_gather; // (the gather counts as device-side time for the split rule)
+        auto helpers = [&](size_t n_items, const std::function<void(size_t, size_t)> &body) {
+            const size_t nt = n_items >= 4096 ? 2 : 1;
+            std::vector<std::thread> th;
+            for (size_t t = 1; t < nt; ++t)
+                th.emplace_back([&, t] { body(n_items * t / nt, n_items * (t + 1) / nt); });
+            body(0, n_items / nt);
+            for (auto &x : th)
+                x.join();
+        };
+        zdst_buf.resize(cap + cap / 8, false);
+        if (sw.dump_packs) { // debugging aid: the packs of this call, for scripts/zstd_gpu_probe.py
+            static int dump_no = 0;
+            const std::string base = sw.dump_packs_dir + "/packs_" + std::to_string(dump_no++);
+            if (FILE *f = fopen((base + ".bin").c_str(), "wb")) {
+                fwrite(zsrc_buf.data(), 1, dr.src_off[nd], f);
+                fclose(f);
+            }
+            if (FILE *f = fopen((base + ".off").c_str(), "wb")) {
+                fwrite(dr.src_off.data(), 8, nd + 1, f);
+                fclose(f);
+            }
+        }
+
+        const bool ok = hip_ok(agc_hip_zstd_batch(hip, (uint32_t)nd, zsrc_buf.data(), dr.src_off.data(), any_ref ? levels.data() : nullptr, zdst_buf.data(), cap,
+                                                  dr.dst_off.data()),
+                               "zstd_batch");
+        dr.t_dev = now() - td;
+        if (ok && !sw.verify_dev_frames) { // (a checking run compares the frames with libzstd's first: settle_device_frames, with the pool)
+            helpers(nd, [&](size_t a, size_t b) {
+                for (size_t t = a; t < b; ++t)
+                    frame_to_job(jobs[dev_jobs[t]], zdst_buf.data() + dr.dst_off[t], (uint32_t)(dr.dst_off[t + 1] - dr.dst_off[t]));
+            });
+            dr.results_done = true;
+        }
+        return ok;
+    });
+}
+
+// AGC_AMD_VERIFY_DEV_FRAMES=1 (a checking aid, e.g. `bench.py --verify-entropy`): every frame the device returned is
+// compressed again by libzstd and compared byte for byte -- the device entropy stage checked at full size, on the very
+// packs of this Close()
+void CAGCCompressor::Impl::verify_device_frames(const std::vector<ZJob> &jobs, const EntropyPlan &plan, const DeviceRound &dr)
+{
+    const std::vector<uint32_t> &dev_jobs = plan.dev_jobs;
+    const std::vector<uint64_t> &dst_off = dr.dst_off;
+    std::atomic<uint64_t> bad{0};
+    zpool->parallel_for(dev_jobs.size(), [&](size_t t, unsigned tid) {
+        const ZJob &j = jobs[dev_jobs[t]];
+        const bytes_t &srcb = j.src();
+        const size_t bound = zstd.compressBound(srcb.size());
+        bytes_t ref(bound + 1);
+        const size_t n = zctx[tid]->compress(ref.data(), bound, srcb.data(), srcb.size(), j.kind == 0 ? j.level : 17);
+        if (n != dst_off[t + 1] - dst_off[t] || memcmp(ref.data(), zdst_buf.data() + dst_off[t], n) != 0)
+            ++bad;
+    });
+    // (frames that came in through CloseProvideFrames were gathered elsewhere: no input offsets here)
+    const uint64_t src_bytes = dr.src_off.empty() ? 0 : dr.src_off[dev_jobs.size()];
+    std::cerr << "verify: " << dev_jobs.size() << " device frames (" << src_bytes / 1e6 << " MB) against libzstd (level 17; references 13 / 19): "
+              << bad.load() << " differ" << std::endl;
+    verify_frames += dev_jobs.size();
+    verify_bad += bad.load();
+    if (bad.load())
+        err("entropy stage: device frames differ from libzstd");
+}
+
+// The end of the device's side: the wait for its thread, libzstd after all when the device refused, the frames into their jobs
+// when the device's thread has not put them there, the stage's counters and the share of the next round.
+void CAGCCompressor::Impl::settle_device_frames(std::vector<ZJob> &jobs, const EntropyPlan &plan, DeviceRound &dr, bool ext, double t_host, RoundLaps &LAP)
+{
+    const std::vector<uint32_t> &dev_jobs = plan.dev_jobs;
+    const std::vector<uint64_t> &src_off = dr.src_off, &dst_off = dr.dst_off;
+    const bool ok = ext ? true : dr.done.get();
+    // (this runs on the entropy thread: its wait is NOT added to st.t_device, which the thread driving the steps reads for
+    // its host-only stage times; t_zstd_dev below is the device call's own time)
+    const double t_dev = dr.t_dev;
+    st.t_zstd_dev += t_dev;
+    LAP("wait for the device");
+    const double ts1 = now();
+    if (!ok) { // the device refused: libzstd does them after all (same bytes)
+        zpool->parallel_for(dev_jobs.size(), [&](size_t t, unsigned tid) {
+            ZJob &j = jobs[dev_jobs[t]];
+            const bytes_t &srcb = j.src();
+            size_t bound = zstd.compressBound(srcb.size());
+            bytes_t packed(bound + 1);
+            uint32_t ps = (uint32_t)zctx[tid]->compress(packed.data(), bound, srcb.data(), srcb.size(), j.kind == 0 ? j.level : 17);
+            frame_to_job(j, packed.data(), ps);
+        });
+        return;
+    }
+    if (sw.verify_dev_frames)
+        verify_device_frames(jobs, plan, dr);
+    if (!dr.results_done)
+        zpool->parallel_for(dev_jobs.size(), [&](size_t t, unsigned) {
+            frame_to_job(jobs[dev_jobs[t]], zdst_buf.data() + dst_off[t], (uint32_t)(dst_off[t + 1] - dst_off[t]));
+        });
+    if (!ext) {
+        st.zstd_dev_in += src_off[dev_jobs.size()];
+        st.zstd_dev_out += dst_off[dev_jobs.size()];
+    }
+    st.t_zstd_stage += now() - ts1;
+    // rates of this call -> share of the next one (only meaningful when both had a real amount of work)
+    if (!ext && src_off[dev_jobs.size()] > (8u << 20) && plan.host_bytes > (8u << 20) && t_dev > 0 && t_host > 0 && !sw.share_fixed) {
+        const double r_dev = src_off[dev_jobs.size()] / t_dev, r_host = plan.host_bytes / t_host;
+        gpu_zstd_share = std::min(0.98, std::max(0.05, r_dev / (r_dev + r_host)));
+    }
+    if (verbosity > 0 && !ext)
+        std::cerr << "entropy stage: device " << src_off[dev_jobs.size()] / 1e6 << " MB in " << t_dev << " s, host " << plan.host_bytes / 1e6 << " MB in "
+                  << t_host << " s; next device share " << gpu_zstd_share << std::endl;
+}
+
+void CAGCCompressor::Impl::run_jobs_round(std::vector<ZJob> &jobs)
+{
+    double t0 = now();
+    RoundLaps LAP{laps_on() && jobs.size() > 0, t0};
+    const bool ext = close_collected && &jobs == &close_jobs; // frames of the collected packs came in through CloseProvideFrames
+    const EntropyPlan plan = plan_entropy_round(jobs, ext);
+    if (LAP.on) {
         uint64_t nb[4] = {0, 0, 0, 0}, nc[4] = {0, 0, 0, 0};
         for (const ZJob &j : jobs) {
-            const int c = j.kind == 0 ? 0 : j.data.size() > dev_max ? 1 : j.data.size() > 16384 ? 2 : 3;
+            const int c = j.kind == 0 ? 0 : j.data.size() > plan.dev_max ? 1 : j.data.size() > 16384 ? 2 : 3;
             nb[c] += j.data.size();
             ++nc[c];
         }
         std::cerr << "    entropy jobs: refs " << nc[0] << " (" << nb[0] / 1e6 << " MB), packs > 128 KiB " << nc[1] << " (" << nb[1] / 1e6 << " MB), packs 16-128 KiB "
-                  << nc[2] << " (" << nb[2] / 1e6 << " MB), packs <= 16 KiB " << nc[3] << " (" << nb[3] / 1e6 << " MB); device gets " << dev_jobs.size() << "\n";
+                  << nc[2] << " (" << nb[2] / 1e6 << " MB), packs <= 16 KiB " << nc[3] << " (" << nb[3] / 1e6 << " MB); device gets " << plan.dev_jobs.size() << "\n";
     }
     LAP("split");
-    std::future<bool> dev_done;
-    bool dev_results_done = false; // (written by the device's thread, read after dev_done.get())
-    std::vector<uint64_t> src_off, dst_off;
+    DeviceRound dr;
     const double ts0 = now();
-    if (ext) {
-        dst_off = close_frames_off; // (zdst_buf holds the frames)
-    } else if (!dev_jobs.empty()) {
-        const size_t nd = dev_jobs.size();
-        src_off.assign(nd + 1, 0);
-        std::vector<uint8_t> levels(nd);
-        bool any_ref = false;
-        for (size_t t = 0; t < nd; ++t) {
-            const ZJob &j = jobs[dev_jobs[t]];
-            src_off[t + 1] = src_off[t] + (j.staged.empty() ? j.data.size() : j.staged.size());
-            levels[t] = j.kind == 0 ? j.level : 17;
-            any_ref = any_ref || j.kind == 0;
-        }
-        const uint64_t cap = src_off[nd] + 32 * nd + 64; // a frame never exceeds its input by more than the headers
-        dst_off.assign(nd + 1, 0);
-        // the packs are gathered by the whole pool (hundreds of MB into fresh pages: a tenth of a second for one thread; the pool's
-        // own jobs wait the 7 ms this takes -- helper threads beside a pool that already uses the whole CPU quota were measured:
-        // the device's side then starts late and ends 57 ms behind the pool), then the device call runs beside the pool's jobs
-        // on a thread of its own, which also puts the frames back into their jobs as soon as the device is done
-        const double tg = now();
-        zsrc_buf.resize(src_off[nd] + src_off[nd] / 8, false); // (headroom: the next call's packs are a little longer)
-        {
-            const size_t n_chunks = std::min<size_t>(nd, (size_t)zpool->size() * 4);
-            zpool->parallel_for(n_chunks, [&](size_t ci, unsigned) {
-                for (size_t t = nd * ci / n_chunks; t < nd * (ci + 1) / n_chunks; ++t) {
-                    const ZJob &j = jobs[dev_jobs[t]];
-                    const bytes_t &srcb = j.staged.empty() ? j.data : j.staged;
-                    memcpy(zsrc_buf.data() + src_off[t], srcb.data(), srcb.size());
-                }
-            });
-        }
-        const double t_gather = now() - tg;
-        dev_done = std::async(std::launch::async, [&, nd, cap, t_gather, levels, any_ref] {
-            const double td = now() - t_gather; // (the gather counts as device-side time for the split rule)
-            auto helpers = [&](size_t n_items, const std::function<void(size_t, size_t)> &body) {
-                const size_t nt = n_items >= 4096 ? 2 : 1;
-                std::vector<std::thread> th;
-                for (size_t t = 1; t < nt; ++t)
-                    th.emplace_back([&, t] { body(n_items * t / nt, n_items * (t + 1) / nt); });
-                body(0, n_items / nt);
-                for (auto &x : th)
-                    x.join();
-            };
-            zdst_buf.resize(cap + cap / 8, false);
-            if (const char *dump = getenv("AGC_AMD_DUMP_PACKS")) { // debugging aid: the packs of this call, for scripts/zstd_gpu_probe.py
-                static int dump_no = 0;
-                const std::string base = std::string(dump) + "/packs_" + std::to_string(dump_no++);
-                if (FILE *f = fopen((base + ".bin").c_str(), "wb")) {
-                    fwrite(zsrc_buf.data(), 1, src_off[nd], f);
-                    fclose(f);
-                }
-                if (FILE *f = fopen((base + ".off").c_str(), "wb")) {
-                    fwrite(src_off.data(), 8, nd + 1, f);
-                    fclose(f);
-                }
-            }
-
-            const bool ok = hip_ok(agc_hip_zstd_batch(hip, (uint32_t)nd, zsrc_buf.data(), src_off.data(), any_ref ? levels.data() : nullptr, zdst_buf.data(), cap,
-                                                      dst_off.data()),
-                                   "zstd_batch");
-            t_dev = now() - td;
-            static const bool verify_dev = getenv("AGC_AMD_VERIFY_DEV_FRAMES") != nullptr;
-            if (ok && !verify_dev) { // (a checking run compares the frames with libzstd's first: below, with the pool)
-                helpers(nd, [&](size_t a, size_t b) {
-                    for (size_t t = a; t < b; ++t) {
-                        ZJob &j = jobs[dev_jobs[t]];
-                        const uint32_t ps = (uint32_t)(dst_off[t + 1] - dst_off[t]);
-                        bytes_t packed(zdst_buf.data() + dst_off[t], zdst_buf.data() + dst_off[t + 1]);
-                        packed.push_back(0);
-                        finish(j, packed, ps, j.kind == 0 ? j.marker : 0);
-                        bytes_t().swap(j.staged);
-                    }
-                });
-                dev_results_done = true;
-            }
-            return ok;
-        });
-    }
+    if (ext)
+        dr.dst_off = close_frames_off; // (zdst_buf holds the frames)
+    else if (!plan.dev_jobs.empty())
+        launch_device_frames(jobs, plan, dr);
     const double th0 = now();
     st.t_zstd_stage += th0 - ts0;
     LAP("gather + launch");
@@ -715,77 +790,14 @@ void CAGCCompressor::Impl::run_jobs_round(std::vector<ZJob> &jobs)
         all_bytes += j.data.size();
     // (... when that thread has human-size samples to drive; a collection of small genomes leaves it idle most of the time)
     const unsigned host_workers = all_bytes < (64u << 20) && heavy_steps && !z_caller_waits.load() ? std::max(2u, zpool->size() / 4) : zpool->size();
-    zpool->parallel_for(host_jobs.size(), [&](size_t hi, unsigned tid) {
-        host_compress(jobs[host_jobs[hi]], tid);
+    zpool->parallel_for(plan.host_jobs.size(), [&](size_t hi, unsigned tid) {
+        host_compress(jobs[plan.host_jobs[hi]], tid);
     }, host_workers);
-    t_host = now() - th0;
+    const double t_host = now() - th0;
     st.t_zstd_host += t_host;
     LAP("host pool");
-    if (!dev_jobs.empty()) {
-        const double t1 = now();
-        const bool ok = ext ? true : dev_done.get();
-        // (this runs on the entropy thread: its wait is NOT added to st.t_device, which the thread driving the steps reads for
-        // its host-only stage times; t_zstd_dev below is the device call's own time)
-        (void)t1;
-        st.t_zstd_dev += t_dev;
-        LAP("wait for the device");
-        const double ts1 = now();
-        if (!ok) { // the device refused: libzstd does them after all (same bytes)
-            zpool->parallel_for(dev_jobs.size(), [&](size_t t, unsigned tid) {
-                ZJob &j = jobs[dev_jobs[t]];
-                const bytes_t &srcb = j.staged.empty() ? j.data : j.staged;
-                size_t bound = zstd.compressBound(srcb.size());
-                bytes_t packed(bound + 1);
-                uint32_t ps = (uint32_t)zctx[tid]->compress(packed.data(), bound, srcb.data(), srcb.size(), j.kind == 0 ? j.level : 17);
-                finish(j, packed, ps, j.kind == 0 ? j.marker : 0);
-            });
-        } else {
-            // AGC_AMD_VERIFY_DEV_FRAMES=1 (a checking aid, e.g. `bench.py --verify-entropy`): every frame the device returned is
-            // compressed again by libzstd and compared byte for byte -- the device entropy stage checked at full size, on the very
-            // packs of this Close()
-            static const bool verify_dev = getenv("AGC_AMD_VERIFY_DEV_FRAMES") != nullptr;
-            if (verify_dev) {
-                std::atomic<uint64_t> bad{0};
-                zpool->parallel_for(dev_jobs.size(), [&](size_t t, unsigned tid) {
-                    const ZJob &j = jobs[dev_jobs[t]];
-                    const bytes_t &srcb = j.staged.empty() ? j.data : j.staged;
-                    const size_t bound = zstd.compressBound(srcb.size());
-                    bytes_t ref(bound + 1);
-                    const size_t n = zctx[tid]->compress(ref.data(), bound, srcb.data(), srcb.size(), j.kind == 0 ? j.level : 17);
-                    if (n != dst_off[t + 1] - dst_off[t] || memcmp(ref.data(), zdst_buf.data() + dst_off[t], n) != 0)
-                        ++bad;
-                });
-                std::cerr << "verify: " << dev_jobs.size() << " device frames (" << src_off[dev_jobs.size()] / 1e6 << " MB) against libzstd (level 17; references 13 / 19): "
-                          << bad.load() << " differ" << std::endl;
-                verify_frames += dev_jobs.size();
-                verify_bad += bad.load();
-                if (bad.load())
-                    err("entropy stage: device frames differ from libzstd");
-            }
-            if (!dev_results_done)
-                zpool->parallel_for(dev_jobs.size(), [&](size_t t, unsigned) {
-                    ZJob &j = jobs[dev_jobs[t]];
-                    const uint32_t ps = (uint32_t)(dst_off[t + 1] - dst_off[t]);
-                    bytes_t packed(zdst_buf.data() + dst_off[t], zdst_buf.data() + dst_off[t + 1]);
-                    packed.push_back(0);
-                    finish(j, packed, ps, j.kind == 0 ? j.marker : 0);
-                    bytes_t().swap(j.staged);
-                });
-            if (!ext) {
-                st.zstd_dev_in += src_off[dev_jobs.size()];
-                st.zstd_dev_out += dst_off[dev_jobs.size()];
-            }
-            st.t_zstd_stage += now() - ts1;
-            // rates of this call -> share of the next one (only meaningful when both had a real amount of work)
-            if (!ext && src_off[dev_jobs.size()] > (8u << 20) && host_bytes > (8u << 20) && t_dev > 0 && t_host > 0 && !getenv("AGC_AMD_GPU_ZSTD_SHARE")) {
-                const double r_dev = src_off[dev_jobs.size()] / t_dev, r_host = host_bytes / t_host;
-                gpu_zstd_share = std::min(0.98, std::max(0.05, r_dev / (r_dev + r_host)));
-            }
-            if (verbosity > 0 && !ext)
-                std::cerr << "entropy stage: device " << src_off[dev_jobs.size()] / 1e6 << " MB in " << t_dev << " s, host " << host_bytes / 1e6 << " MB in "
-                          << t_host << " s; next device share " << gpu_zstd_share << std::endl;
-        }
-    }
+    if (!plan.dev_jobs.empty())
+        settle_device_frames(jobs, plan, dr, ext, t_host, LAP);
     LAP("results -> jobs");
     st.t_zstd += now() - t0;
 }
@@ -925,7 +937,7 @@ bool CAGCCompressor::Impl::batch_prepare(BatchState &b, std::vector<Contig> &ctg
     if (b.needs_turn)
         return true;
     b.n_samples = ctgs.empty() ? 1u : ctgs.back().sample_idx + 1;
-    b.overlap_encode = overlap_mode != 0 && b.n_samples == 1 && !always_speculate;
+    b.overlap_encode = sw.overlap_mode != 0 && b.n_samples == 1 && !always_speculate;
     b.subset.resize(seg_buf.size());
     std::iota(b.subset.begin(), b.subset.end(), 0u);
     if (!stage_classify(b) || !stage_place(b))
@@ -1154,8 +1166,7 @@ bool CAGCCompressor::Impl::revalidate(BatchState &b)
 // AGC_AMD_LAPS=1: wall time of every host sub-stage of a registration on stderr (profiling aid)
 void CAGCCompressor::Impl::lap(BatchState &b, const char *what)
 {
-    static const bool laps = getenv("AGC_AMD_LAPS") != nullptr;
-    if (!laps)
+    if (!laps_on())
         return;
     std::cerr << "  lap " << what << " " << (now() - b.lap_t) * 1e3 << " ms\n";
     b.lap_t = now();
@@ -1171,7 +1182,7 @@ void CAGCCompressor::Impl::lap(BatchState &b, const char *what)
 // mode (the prepare ahead of the turn).
 bool CAGCCompressor::Impl::use_dev_segments(const BatchState &b) const
 {
-    return dev_segments && b.pk.n_symbols && k >= 16 && b.n_ctg && overlap_mode == 0;
+    return sw.dev_segments && b.pk.n_symbols && k >= 16 && b.n_ctg && sw.overlap_mode == 0;
 }
 
 // -> 1 done, 0 failed, 2 the window goes the host's way (adaptive mode: new splitters were mined; they wait in b.mined_*)
@@ -1214,8 +1225,8 @@ int CAGCCompressor::Impl::stage_scan_dev(BatchState &b)
             }
         }
     } pre{this};
-    const bool pre_enc = pre_launch_encode && async_encode && book_can_async(1) && b.base_owned && ctgs.back().sample_idx == 0 && !adaptive && dist_world == 1 &&
-                         (ctg_off[n_ctg] - ctg_off[0]) / std::max<uint64_t>(segment_size, 1) >= (uint64_t)dev_encode_min;
+    const bool pre_enc = sw.pre_launch_encode && sw.async_encode && book_can_async(1) && b.base_owned && ctgs.back().sample_idx == 0 && !adaptive && dist_world == 1 &&
+                         (ctg_off[n_ctg] - ctg_off[0]) / std::max<uint64_t>(segment_size, 1) >= (uint64_t)sw.dev_encode_min;
     if (pre_enc) {
         lane2_acquire(); // (the previous sample's deltas were collected by its early task long ago)
         pre.armed = true;
@@ -1249,10 +1260,10 @@ int CAGCCompressor::Impl::stage_scan_dev(BatchState &b)
     // collected beside the next sample (bookkeeping thread); otherwise the commit encodes as before
     // (... and when the sample is large enough to fill the GPU with one wavefront per segment: the few dozen segments of a bacterial
     // genome are encoded from the host's descriptors at commit time instead, where the library parses them in chunks)
-    const bool enc = async_encode && book_can_async(1) && b.base_owned && ctgs.back().sample_idx == 0 && n_segs >= dev_encode_min;
+    const bool enc = sw.async_encode && book_can_async(1) && b.base_owned && ctgs.back().sample_idx == 0 && n_segs >= sw.dev_encode_min;
     std::vector<uint8_t> is_known(enc ? n_segs : 0, 0);
     {
-        const size_t n_chunks = n_segs >= par_min ? std::min<size_t>(std::max<size_t>(n_segs / 2048, 2), (size_t)pool->size() * 4) : 1;
+        const size_t n_chunks = n_segs >= sw.par_min ? std::min<size_t>(std::max<size_t>(n_segs / 2048, 2), (size_t)pool->size() * 4) : 1;
         auto conv = [&](size_t ci, unsigned) {
             for (size_t i = n_segs * ci / n_chunks; i < n_segs * (ci + 1) / n_chunks; ++i) {
                 const agc_hip_segment &d = dsegs[i];
@@ -1417,7 +1428,7 @@ int CAGCCompressor::Impl::stage_scan_dev(BatchState &b)
             }
             return {text, ref};
         };
-        if (spec_fill_ahead > 0 && (n_segs >= 4096 || spec_fill_ahead > 1))
+        if (sw.spec_fill_ahead > 0 && (n_segs >= 4096 || sw.spec_fill_ahead > 1))
             b.spec_fill = std::async(std::launch::async, std::move(fill));
         else {
             const auto tr = fill();
@@ -1456,7 +1467,7 @@ bool CAGCCompressor::Impl::launch_known_encode(BatchState &b, bool launched_alre
             // is then free long before the next sample's launch asks for it (it used to be released by the registration's own
             // task, a whole step later: 0.9 ms of "second lane free" per human-size sample) and that task starts with its deltas
             // on the host.  enc_buf is nobody's until the hand-over swaps the buffer sets (bulk mode: spec_bytes == 0).
-            if (early_collect && dist_world == 1 && book_can_async(1) && b.spec_bytes == 0) {
+            if (sw.early_collect && dist_world == 1 && book_can_async(1) && b.spec_bytes == 0) {
                 const uint64_t text = b.known_text;
                 std::unique_ptr<BookTask> t(new BookTask());
                 t->early_only = true;
@@ -1660,7 +1671,7 @@ bool CAGCCompressor::Impl::stage_scan(BatchState &b)
                 }
             }
         };
-        if (segs.size() >= par_min)
+        if (segs.size() >= sw.par_min)
             pool->parallel_for(n_chunks, fill);
         else
             for (size_t ci = 0; ci < n_chunks; ++ci)
@@ -1689,7 +1700,7 @@ bool CAGCCompressor::Impl::stage_classify(BatchState &b)
     // (a) per segment, independent of the others: reset of the classification fields, the key of a segment with both splitters
     // and its look-up in the map -- 50 k records and as many probes of a table that does not fit the caches: the pool
     {
-        const size_t nL = L.size(), n_chunks = nL >= par_min ? std::min<size_t>(std::max<size_t>(nL / 2048, 2), (size_t)pool->size() * 4) : 1;
+        const size_t nL = L.size(), n_chunks = nL >= sw.par_min ? std::min<size_t>(std::max<size_t>(nL / 2048, 2), (size_t)pool->size() * 4) : 1;
         auto reset_chunk = [&](size_t ci, unsigned) {
             for (size_t t = nL * ci / n_chunks; t < nL * (ci + 1) / n_chunks; ++t) {
                 Seg &s = segs[L[t]];
@@ -1772,7 +1783,7 @@ bool CAGCCompressor::Impl::stage_classify(BatchState &b)
     t0 = now();
 
     LAP("keys");
-    if (b.overlap_encode && overlap_mode == 1 && !overlap_encode_begin(b))
+    if (b.overlap_encode && sw.overlap_mode == 1 && !overlap_encode_begin(b))
         return false;
     LAP("encode_begin");
     // ---- GPU: estimates for every (one-splitter segment, candidate) pair ----
@@ -1870,7 +1881,7 @@ bool CAGCCompressor::Impl::stage_classify(BatchState &b)
     {
         // the segments are independent here (the map and the terminator lists are only read): chunks of the list go to the pool,
         // the jobs they produce are numbered afterwards in segment order
-        const size_t nL = L.size(), n_chunks = nL >= par_min ? std::min<size_t>(std::max<size_t>(nL / 1024, 2), (size_t)pool->size() * 4) : 1;
+        const size_t nL = L.size(), n_chunks = nL >= sw.par_min ? std::min<size_t>(std::max<size_t>(nL / 1024, 2), (size_t)pool->size() * 4) : 1;
         std::vector<std::vector<MidJob>> chunk_jobs(n_chunks);
         std::vector<uint64_t> chunk_tried(n_chunks, 0);
         std::vector<uint8_t> chunk_bad(n_chunks, 0);
@@ -1979,7 +1990,7 @@ bool CAGCCompressor::Impl::stage_classify(BatchState &b)
     // meanwhile: the group map and the segments are this thread's, and this thread is inside the device call.
     std::future<void> place_helper;
     b.place_ahead_valid = false;
-    if (place_ahead > 0 && !mids.empty() && (segs.size() >= 4096 || place_ahead > 1)) {
+    if (sw.place_ahead > 0 && !mids.empty() && (segs.size() >= 4096 || sw.place_ahead > 1)) {
         b.place_ahead.resize(segs.size());
         b.place_ahead_ok.assign(segs.size(), 0);
         place_helper = std::async(std::launch::async, [this, &b, &segs, &ctgs] {
@@ -2076,7 +2087,7 @@ bool CAGCCompressor::Impl::stage_place(BatchState &b)
     // the announced next sample: its expansion + scan are queued NOW -- the classification kernels of this sample are done, what
     // follows is host work (placement, ordering, new group ids: ~2.5 ms at human scale) before the encode needs the GPU again
     launch_prefetch();
-    if (b.overlap_encode && overlap_mode == 2 && !b.enc_in_flight && !overlap_encode_begin(b))
+    if (b.overlap_encode && sw.overlap_mode == 2 && !b.enc_in_flight && !overlap_encode_begin(b))
         return false;
     // ---- add_segment, part 4: final placement + part numbers ----
     std::vector<Placed> &placed = placed_buf;
@@ -2423,7 +2434,7 @@ bool CAGCCompressor::Impl::stage_store_head(BatchState &b)
     // them (finish_ref_store) -- a one-block kernel queued behind the announced scan and the FASTA conversion took 1.4 ms to come
     // back, three round trips a step.  The reference sample's GBs of new references take the calls below as before.
     bool ref_async = false;
-    if (ref_store_async && dist_world == 1 && book_can_async(b.n_samples) && b.pk.n_symbols && new_ref_items.size() + raw_items.size() > 0) {
+    if (sw.ref_store_async && dist_world == 1 && book_can_async(b.n_samples) && b.pk.n_symbols && new_ref_items.size() + raw_items.size() > 0) {
         const size_t nr = new_ref_items.size(), nf = nr + raw_items.size();
         uint64_t tot = 0;
         for (size_t i = 0; i < nf; ++i)
@@ -2667,7 +2678,7 @@ bool CAGCCompressor::Impl::stage_store_finish(BatchState &b)
             // The encode is only LAUNCHED here when its result is first read by the bookkeeping task: the task collects it (second
             // device lane) while this thread goes on with the next sample.  Needs a sample in a staging buffer the device context
             // owns (it outlives the call) and nothing else on that lane.
-            const bool later = hand_over && async_encode && dist_world == 1 && b.base_owned && b.pk.n_symbols && overlap_mode == 0 && !b.enc_in_flight && b.spec_bytes == 0;
+            const bool later = hand_over && sw.async_encode && dist_world == 1 && b.base_owned && b.pk.n_symbols && sw.overlap_mode == 0 && !b.enc_in_flight && b.spec_bytes == 0;
             if (!bulk && later) {
                 lane2_acquire();
                 if (!hip_ok(DEVT(agc_hip_lz_encode_begin_packed(hip, (uint32_t)ne, gid.data(), &b.pk, off.data(), len.data(), rc.data())), "lz_encode_begin")) {
@@ -2927,7 +2938,7 @@ bool CAGCCompressor::Impl::book_and_store(CommitData &cdta)
         };
         // groups are independent of each other (the reference runs them on all worker threads,
         // agc_compressor.cpp:989-1050): big samples go to the pool in chunks, jobs merged in list order
-        if (sl.n_lists() >= par_min) {
+        if (sl.n_lists() >= sw.par_min) {
             const size_t n_chunks = std::min<size_t>(sl.n_lists(), (size_t)wp->size() * 8);
             std::vector<std::vector<ZJob>> chunk_jobs(n_chunks);
             defer_stream_reg = true;
@@ -3008,14 +3019,7 @@ bool CAGCCompressor::Impl::book_and_store(CommitData &cdta)
         // the archive waits in host memory (ArchiveWriter writes its events in order) -- past the ceiling (a quarter of the
         // machine's memory, 16 GiB at most; round 5: 2 GiB, which the first fill of 50 k human packs at -b 100 overran) the
         // writer's own entropy stage takes what has piled up and the archive flows again.
-        static const uint64_t defer_cap = []() -> uint64_t {
-            if (const char *e = getenv("AGC_AMD_DEFER_MAX_MB"))
-                return (uint64_t)strtoull(e, nullptr, 10) << 20;
-            const long pages = sysconf(_SC_PHYS_PAGES), psz = sysconf(_SC_PAGE_SIZE);
-            const uint64_t quarter = pages > 0 && psz > 0 ? (uint64_t)pages * (uint64_t)psz / 4 : (4ull << 30);
-            return std::min<uint64_t>(16ull << 30, std::max<uint64_t>(2ull << 30, quarter));
-        }();
-        if (deferred_bytes > defer_cap) {
+        if (deferred_bytes > sw.defer_cap) { // (AGC_AMD_DEFER_MAX_MB)
             for (ZJob &j : deferred_packs)
                 now_jobs.emplace_back(std::move(j));
             deferred_packs.clear();
@@ -3024,7 +3028,7 @@ bool CAGCCompressor::Impl::book_and_store(CommitData &cdta)
         all_jobs.swap(now_jobs);
     }
     z_submit(std::move(all_jobs));
-    if (sync_entropy)
+    if (sw.sync_entropy)
         z_wait_all();
     return true;
 }
@@ -3066,7 +3070,6 @@ void CAGCCompressor::Impl::finish_groups()
         close_collected = false;
         return;
     }
-    static const bool laps = getenv("AGC_AMD_LAPS") != nullptr;
     const double tl0 = now();
     std::vector<ZJob> jobs;
     build_close_jobs(jobs);
@@ -3086,7 +3089,7 @@ void CAGCCompressor::Impl::finish_groups()
         jobs.emplace_back(std::move(j));
     deferred_packs.clear();
     z_caller_waits = true;     // (Close waits for the entropy thread, then flushes)
-    if (laps)
+    if (laps_on())
         std::cerr << "    finish_groups: pack jobs " << (tl1 - tl0) * 1e3 << " ms, their places in the archive " << (now() - tl1) * 1e3 << " ms\n";
     z_submit(std::move(jobs));
 }

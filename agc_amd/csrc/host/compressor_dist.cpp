@@ -182,7 +182,7 @@ bool CAGCCompressor::Impl::make_record_body(const CommitData &cd)
                 memcpy(d + 4, cd.enc_ptr[ei], n);
         }
     };
-    if (nb >= par_min) {
+    if (nb >= sw.par_min) {
         const size_t n_chunks = std::min<size_t>(nb, (size_t)pool->size() * 4);
         pool->parallel_for(n_chunks, [&](size_t ci, unsigned) { copy_range(nb * ci / n_chunks, nb * (ci + 1) / n_chunks); });
     } else

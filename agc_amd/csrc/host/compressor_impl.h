@@ -4,6 +4,7 @@
 #pragma once
 #include "compressor.h"
 #include "host_support.h"
+#include "switches.h"
 #include <list>
 #include <cerrno>
 #include <fcntl.h>
@@ -348,11 +349,10 @@ struct PinnedBytes {
         if (!keep)
             release();
         void *q = nullptr;
-        static const bool laps = getenv("AGC_AMD_LAPS") != nullptr;
         const auto t0 = std::chrono::steady_clock::now();
         const size_t had = n;
         const bool pin = ctx && agc_hip_host_alloc(ctx, m, &q) == AGC_HIP_OK && q;
-        if (laps && m >= (4u << 20))
+        if (laps_on() && m >= (4u << 20))
             fprintf(stderr, "    pinned buffer: %.1f -> %.1f MB in %.3f ms\n", had / 1e6, m / 1e6,
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
         if (!pin)
@@ -404,6 +404,7 @@ struct ZJob { // one archive part to produce
     bytes_t out;
     uint64_t meta = 0;
     std::shared_ptr<PartSlot> slot; // asynchronous entropy stage: where the finished part goes (already queued in the archive)
+    const bytes_t &src() const { return staged.empty() ? data : staged; } // what the encoder reads
 };
 
 // bytes2tuples, src/common/segment.h:73-138
@@ -631,6 +632,23 @@ public:
         munmap(m, n);
         return true;
     }
+    // A whole file: through the mapped reader when it qualifies (read_all_mapped), else record by record.  false: it cannot be opened.
+    static bool read_file(const std::string &fn, std::vector<std::string> &ids, std::vector<bytes_t> &ctgs, unsigned n_threads, uint64_t map_min)
+    {
+        if (read_all_mapped(fn, ids, ctgs, n_threads, map_min))
+            return true;
+        FastaReader fr;
+        if (!fr.open(fn))
+            return false;
+        std::string id;
+        bytes_t contig;
+        while (fr.read_contig_raw(id, contig)) {
+            ids.emplace_back(id);
+            ctgs.emplace_back(std::move(contig));
+            contig.clear();
+        }
+        return true;
+    }
     bool read_contig_raw(std::string &id, bytes_t &ctg)
     {
         id.clear();
@@ -797,9 +815,7 @@ struct CAGCCompressor::Impl {
     std::deque<std::vector<ZJob>> z_queue;
     bool z_busy = false, z_stop = false;
     std::atomic<bool> z_caller_waits{false}; // the caller stands still for the stage (Close, Drain): its launches may take the LDS
-    bool sync_entropy = false;
     std::atomic<bool> heavy_steps{false};    // the windows being driven are human-size: the entropy thread takes a quarter of the pool for small batches
-    size_t par_min = 4096; // lists shorter than this are walked by the calling thread (AGC_AMD_PAR_MIN: tests force the pool paths)
     void z_submit(std::vector<ZJob> &&jobs);
     void z_wait_all();
     void z_main();
@@ -864,13 +880,10 @@ struct CAGCCompressor::Impl {
     std::condition_variable book_cv, book_idle_cv;
     std::deque<std::unique_ptr<BookTask>> book_queue;
     bool book_busy = false, book_stop = false, book_failed = false;
-    bool async_book = true, async_encode = true;
-    bool early_collect = true; // the whole-sample encode is collected by an early task of the book thread (AGC_AMD_EARLY_COLLECT=0: by the registration's own)
     uint64_t book_seq_submitted = 0, book_seq_done = 0; // tasks are numbered; they complete in order
     uint64_t last_own_seq = 0;          // the last task that points into this object's buffers (the *_alt set below)
     PinnedBytes ref_pin[2];             // staging of agc_hip_ref_store_begin_packed, alternating (the previous one is the queued task's)
     uint32_t ref_pin_next = 0;
-    bool ref_store_async = true;        // AGC_AMD_REF_STORE_ASYNC=0: lag counters and symbols are waited for where they are asked for
     bool finish_ref_store(CommitData &cd, bytes_t &fetched_dst); // waits for the slot, makes cd.repetitive and cd.fetched
     struct EarlyEnc {                   // result of an early_only task (written by the book thread, read after book_wait_seq)
         bool ok = false;
@@ -880,7 +893,7 @@ struct CAGCCompressor::Impl {
     uint64_t book_delta_bytes = 0;      // deltas collected by the book thread (added to st.delta_bytes by book_wait)
     std::unique_ptr<ThreadPool> bpool;  // the stage's own workers (`pool` belongs to the thread that drives the steps)
     std::mutex coll_mtx;
-    bool book_can_async(uint32_t n_samples) const { return async_book && !appending && !concatenated && !sync_entropy && n_samples == 1; }
+    bool book_can_async(uint32_t n_samples) const { return sw.async_book && !appending && !concatenated && !sw.sync_entropy && n_samples == 1; }
     uint64_t book_submit(std::unique_ptr<BookTask> &&t);
     void book_main();
     bool book_wait();
@@ -994,15 +1007,10 @@ struct CAGCCompressor::Impl {
     bool launch_known_encode(BatchState &b, bool launched_already = false);
     void finish_spec_fill(BatchState &b);
     int stage_scan_dev(BatchState &b);
-    int spec_fill_ahead = 1;           // the table of speculative deltas of the whole-sample encode filled by a helper thread (AGC_AMD_SPEC_FILL_AHEAD=0: in line; 2: any size)
-    int place_ahead = 1;               // placement of the segments without a split-point job beside the wait for the split points (AGC_AMD_PLACE_AHEAD=0: after it; 2: for windows of any size -- tests)
-    bool pre_launch_encode = true;     // the whole-sample encode launched inside agc_hip_segments_packed (AGC_AMD_PRE_LAUNCH_ENCODE=0: behind the table)
-    uint32_t dev_encode_min = 2048;    // segments a sample needs for the device-launched whole-sample encode (AGC_AMD_DEV_ENCODE_MIN: tests)
     bool use_dev_segments(const BatchState &b) const;
     // adaptive mode with windows of several registrations: only where the device delivers the segments (the cut of a window at
     // the registration that brings new splitters lives there)
-    bool adaptive_windows() const { return adaptive && dev_segments && k >= 16 && overlap_mode == 0 && !appending; }
-    bool dev_segments = true;          // AGC_AMD_DEV_SEGMENTS=0: scan hits to the host, cut and key look-up there (the round-3 path)
+    bool adaptive_windows() const { return adaptive && sw.dev_segments && k >= 16 && sw.overlap_mode == 0 && !appending; }
     PinnedBytes dev_seg_buf;           // (pinned: the segment table of a human sample is 3 MB per step)
     // the device's second LZ lane carries one encode at a time: launched by the thread that drives the steps, collected by the
     // bookkeeping thread (or by the driver itself on the synchronous path)
@@ -1018,10 +1026,6 @@ struct CAGCCompressor::Impl {
     bool spec_encode(BatchState &b);
     bool overlap_encode_begin(BatchState &b);
     bool overlap_encode_end(BatchState &b);
-    // AGC_AMD_ENCODE_OVERLAP: off (default) | early (from the key lookup on) | late (from the placement on).  Measured on the
-    // 3 Gbp step: the encode kernel hidden behind estimates / split points costs those kernels what it saves (27.8 ms per step
-    // off, 26.4-29.6 ms early), so the default keeps the kernels one after the other and their timings clean
-    int overlap_mode = 0;
     bool revalidate(BatchState &b);
     bool batch_prepare(BatchState &b, std::vector<Contig> &ctgs, const uint8_t *d_base, const std::vector<bytes_t> *host_data, bool always_speculate);
     bool batch_commit(BatchState &b, uint32_t &n_committed);
@@ -1070,12 +1074,11 @@ struct CAGCCompressor::Impl {
     // share of the pack bytes the device takes when both engines run (AGC_AMD_GPU_ZSTD_SHARE fixes it); the start value is the
     // ratio measured on MI355X + 16 host threads (0.7 GB/s against 0.1 GB/s), every call with real work on both sides updates it
     double gpu_zstd_share = 0.88;
-    uint32_t gpu_zstd_min = 64;        // fewer packs than this in one call stay on the host (AGC_AMD_GPU_ZSTD_MIN)
     // references (level 13 on their tuples, level 19 for repetitive ones) on the device too when a call brings at least this many:
     // the reference sample's ~50 k references take 0.41 s instead of 0.95 s on 16 host threads.  On since round 4: configs[2] at
     // full size with 5 samples is byte-identical to the reference CLI's archive with it (profiles/r4/c3_full_size_identity_5_samples_
-    // refs_on_device.log: 741 MB of the 3.2 GB of entropy input on the device).  AGC_AMD_GPU_ZSTD_REFS=0 keeps them on the host pool.
-    uint32_t gpu_zstd_refs_min = 512;
+    // refs_on_device.log: 741 MB of the 3.2 GB of entropy input on the device).  AGC_AMD_GPU_ZSTD_REFS=0 keeps them on the host pool
+    // (sw.gpu_zstd_refs_min).
     PinnedBytes zsrc_buf, zdst_buf;    // staging of the device entropy stage (plain malloc: no zero fill of hundreds of MB)
     bool defer_stream_reg = false;     // parallel bookkeeping: pack jobs leave a missing delta stream to the merging thread
     bool minted_since_prepare = false; // a group of any key (also one-sided) was minted while a sample was prepared
@@ -1114,11 +1117,38 @@ struct CAGCCompressor::Impl {
     void note_new_group(const pk_t &pk, uint32_t gid);
     void finish_groups();
     void run_jobs(std::vector<ZJob> &jobs, bool add_parts = true);
+    // One entropy round: plan (which frames the device takes) -> launch (gather, device call on a thread of its own) -> host pool
+    // -> settle (wait, verify, frames back into their jobs, the next round's share).
     void run_jobs_round(std::vector<ZJob> &jobs);
-    bool host_only_batch(const std::vector<ZJob> &jobs) const; // run_jobs_round would leave every job of it to the host pool
+    struct EntropyPlan {
+        std::vector<uint32_t> dev_jobs, host_jobs; // indices into the round's jobs; host_jobs longest first
+        uint64_t host_bytes = 0;                   // pack bytes of host_jobs
+        uint32_t dev_max = 0;                      // longest input the device stage takes (0: no device stage)
+    };
+    struct DeviceRound { // the device's side of a round; the device's thread writes it, the entropy thread reads it after done.get()
+        std::future<bool> done;
+        bool results_done = false; // the frames are in their jobs already
+        std::vector<uint64_t> src_off, dst_off;
+        double t_dev = 0;
+    };
+    struct RoundLaps { // AGC_AMD_LAPS: the parts of a round on stderr
+        bool on;
+        double lt;
+        void operator()(const char *what)
+        {
+            if (on)
+                std::cerr << "    entropy lap " << what << " " << (now() - lt) * 1e3 << " ms\n";
+            lt = now();
+        }
+    };
+    EntropyPlan plan_entropy_round(std::vector<ZJob> &jobs, bool ext);
+    void launch_device_frames(std::vector<ZJob> &jobs, const EntropyPlan &plan, DeviceRound &dr);
+    void verify_device_frames(const std::vector<ZJob> &jobs, const EntropyPlan &plan, const DeviceRound &dr);
+    void settle_device_frames(std::vector<ZJob> &jobs, const EntropyPlan &plan, DeviceRound &dr, bool ext, double t_host, RoundLaps &LAP);
+    static void frame_to_job(ZJob &j, const uint8_t *frame, uint32_t n); // a finished frame becomes the job's part
+    bool host_only_batch(const std::vector<ZJob> &jobs) const; // plan_entropy_round would leave every job of it to the host pool
     void host_compress(ZJob &j, unsigned tid);                 // one job through libzstd (zctx[tid])
     void run_host_stream(std::vector<ZJob> &&first);           // z_main: host-only batches without a barrier between them
-    bool entropy_stream = true;                                // (AGC_AMD_ENTROPY_STREAM=0: a parallel_for per batch, as before)
     void build_close_jobs(std::vector<ZJob> &jobs);
     void store_open_batch(bool flush = true);
     // Close in steps (multi-GPU entropy stage, compressor.h: CloseCollectPacks / CloseProvideFrames)
@@ -1148,7 +1178,11 @@ struct CAGCCompressor::Impl {
     std::vector<uint32_t> close_dev_jobs;      // indices in close_jobs of the packs handed out
     std::vector<uint64_t> close_src_off, close_frames_off;
     bool close_collected = false;
+    Switches sw;                       // the AGC_AMD_* switches, read once per session (open_session)
+    bool open_session(unsigned no_threads); // what Create and Append share: device context, pools, zstd contexts, pinned buffers, switches
     void choose_entropy_stage();
+    // determine_splitters on the device for contigs in HBM (sorted_kmers: adaptive mode, every k-mer of them sorted as well)
+    bool splitters_of(const uint8_t *d_codes, const uint64_t *off, uint32_t n_ctg, std::vector<uint64_t> &spl, std::vector<uint64_t> *sorted_kmers);
     void add_job_parts(std::vector<ZJob> &jobs, size_t from, size_t to);
     void make_pack_job(std::vector<ZJob> &jobs, uint32_t gid, bytes_t &data, std::vector<uint32_t> &off);
     PinnedBytes enc_buf, enc_buf2; // grown, never shrunk (enc_buf: the window's speculative deltas, enc_buf2: per commit run); pinned

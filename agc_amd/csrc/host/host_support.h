@@ -95,6 +95,13 @@ struct ZstdCtx {
     size_t compress(uint8_t *dst, size_t cap, const uint8_t *src, size_t n, int level) { return api->compressCCtx(cctx, dst, cap, src, n, level); }
 };
 
+// AGC_AMD_LAPS=1 (a measuring aid, process-wide): wall time of the host's sub-stages on stderr
+inline bool laps_on()
+{
+    static const bool on = getenv("AGC_AMD_LAPS") != nullptr;
+    return on;
+}
+
 // AGC_AMD_START_LAPS=1 (a measuring aid, scripts/start_cost.py): milliseconds since the first call at the named points of a run's start
 inline void start_lap(const char *what)
 {

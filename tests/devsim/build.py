@@ -53,7 +53,7 @@ def _build(force=False):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-Wall", "-c", zsim, "-o", zo])
         subprocess.check_call(["g++", "-shared"] + objs + [zo, "-o", SIM_HIP])
     host_src = [os.path.join(HOST, s) for s in ("compressor.cpp", "compressor_batch.cpp", "compressor_dist.cpp", "capi_host.cpp", "reader.cpp")]
-    host_dep = host_src + [os.path.join(HOST, s) for s in ("compressor.h", "compressor_impl.h", "host_support.h", "reader.h", "archive_read.h")] + [SIM_HIP]
+    host_dep = host_src + [os.path.join(HOST, s) for s in ("compressor.h", "compressor_impl.h", "host_support.h", "switches.h", "reader.h", "archive_read.h")] + [SIM_HIP]
     common = ["g++", "-O2", "-std=c++17", "-fPIC", "-Wall", "-pthread"]
     if force or not _newer(SIM_HOST, host_dep):
         subprocess.check_call(common + ["-shared"] + host_src + ["-o", SIM_HOST, "-L" + OUT, "-lagc_hip", "-Wl,-rpath,$ORIGIN", "-lz", "-ldl"])

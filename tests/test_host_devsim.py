@@ -49,6 +49,14 @@ def test_append_writes_the_reference_archive(cli, plan, tmp_path):
     assert [hashlib.sha256(x).hexdigest() for x in got] == [w["sha256"] for w in want]
 
 
+def test_append_takes_the_same_switches_as_create(cli, tmp_path):
+    """create and append share their session setup: an append plan under non-default switches (every sample takes the
+    device-launched encode, every registration a window of its own, bookkeeping on the calling thread) writes the recorded archives"""
+    env = dict(os.environ, AGC_AMD_DEV_ENCODE_MIN="0", AGC_AMD_WINDOW_MAX="1", AGC_AMD_ASYNC_BOOK="0")
+    got = C.run_append_plan(cli, "adaptive_1_2_4", str(tmp_path), env=env)
+    assert [hashlib.sha256(x).hexdigest() for x in got] == [w["sha256"] for w in GOLD_APPEND["adaptive_1_2_4"]]
+
+
 def test_append_round_trips_through_the_reader(cli, tmp_path):
     from agc_amd import build, reader
     from tests.test_read_cpu import fasta_text, parse_fasta
