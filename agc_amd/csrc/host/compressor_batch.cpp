@@ -285,32 +285,8 @@ void CAGCCompressor::Impl::book_main()
         // the registration's LZ encodes were left in flight on the device's lanes: collect them (only a lane's own state is touched)
         auto collect = [&](uint32_t lane, const std::vector<uint32_t> &todo, uint64_t text, PinnedBytes &enc) {
             const size_t ne = todo.size();
-            std::vector<uint64_t> eoff(ne + 1, 0);
-            {
-                uint32_t n_dev = 0;
-                ok = hip_ok(agc_hip_lz_encode_pending_on(hip, lane, &n_dev), "lz_encode_pending");
-                if (ok && n_dev != ne) {
-                    err("internal: the device's encode delivers another number of deltas than the host expects");
-                    ok = false;
-                }
-            }
-            if (ok) {
-                uint64_t cap = delta_cap(enc.size(), text);
-                for (;;) {
-                    if (!enc.resize(cap, false)) {
-                        err("out of memory (delta buffer)");
-                        ok = false;
-                        break;
-                    }
-                    const int r = agc_hip_lz_encode_end_on(hip, lane, enc.data(), cap, eoff.data());
-                    if (r == AGC_HIP_ECAP) {
-                        cap = eoff[ne] + eoff[ne] / 8 + 4096; // (headroom: the next sample's deltas are a little longer)
-                        continue;
-                    }
-                    ok = hip_ok(r, "lz_encode_end");
-                    break;
-                }
-            }
+            std::vector<uint64_t> eoff;
+            ok = collect_lane((int)lane, enc, 0, delta_cap(enc.size(), text), ne, eoff);
             lane2_release((int)lane); // (the thread that drives the steps may launch the next sample's encode)
             if (ok) {
                 for (size_t i = 0; i < ne; ++i) {
@@ -325,31 +301,8 @@ void CAGCCompressor::Impl::book_main()
         if (t->early_only) {
             // lane 0's deltas as they are, nothing mapped: the registration's own task does that (enc_collected)
             const size_t ne = t->enc_n;
-            std::vector<uint64_t> eoff(ne + 1, 0);
-            uint32_t n_dev = 0;
-            ok = hip_ok(agc_hip_lz_encode_pending_on(hip, 0, &n_dev), "lz_encode_pending");
-            if (ok && n_dev != ne) {
-                err("internal: the device's encode delivers another number of deltas than the host expects");
-                ok = false;
-            }
-            if (ok) {
-                PinnedBytes &enc = *t->enc_dst;
-                uint64_t cap = delta_cap(enc.size(), t->enc_text);
-                for (;;) {
-                    if (!enc.resize(cap, false)) {
-                        err("out of memory (delta buffer)");
-                        ok = false;
-                        break;
-                    }
-                    const int r = agc_hip_lz_encode_end_on(hip, 0, enc.data(), cap, eoff.data());
-                    if (r == AGC_HIP_ECAP) {
-                        cap = eoff[ne] + eoff[ne] / 8 + 4096;
-                        continue;
-                    }
-                    ok = hip_ok(r, "lz_encode_end");
-                    break;
-                }
-            }
+            std::vector<uint64_t> eoff;
+            ok = collect_lane(0, *t->enc_dst, 0, delta_cap(t->enc_dst->size(), t->enc_text), ne, eoff);
             lane2_release(0);
             if (laps_on())
                 std::cerr << "    book task (early): lane 0 collected in " << (now() - t0) * 1e3 << " ms\n";
@@ -970,13 +923,78 @@ bool CAGCCompressor::Impl::batch_commit(BatchState &b, uint32_t &n_committed)
     return true;
 }
 
+// ---- the encode-call layer: job list, the call with its grow-and-retry loop, the collection of a lane ----
+// placed items -> the jobs of one call; book: their symbols go to the encode statistics
+CAGCCompressor::Impl::EncodeJobs CAGCCompressor::Impl::encode_jobs(const std::vector<uint32_t> &items, bool book)
+{
+    EncodeJobs j;
+    for (uint32_t idx : items) {
+        const Placed &pl = placed_buf[idx];
+        j.add((uint32_t)pl.gid, pl.off, pl.len, pl.rc);
+        if (!book)
+            continue;
+        st.enc_text += pl.len;
+        st.enc_ref += groups[pl.gid].ref_size ? groups[pl.gid].ref_size - 1 : 0;
+    }
+    return j;
+}
+
+// The jobs are encoded now, their deltas go to dst[base..) (what lies in front of base stays), eoff[i] is where delta i begins.
+// A buffer too small answers ECAP with the size needed: once more with that plus headroom (the next sample's deltas are a
+// little longer, and every retry runs the kernel again).
+bool CAGCCompressor::Impl::encode_now(BatchState &b, const EncodeJobs &j, PinnedBytes &dst, uint64_t base, uint64_t first_cap, std::vector<uint64_t> &eoff)
+{
+    eoff.assign((size_t)j.n() + 1, 0);
+    for (uint64_t cap = first_cap;;) {
+        if (!dst.resize(base + cap, base != 0)) {
+            err("out of memory (delta buffer)");
+            return false;
+        }
+        const int r = b.pk.n_symbols ? DEVT(agc_hip_lz_encode_batch_packed(hip, j.n(), j.gid.data(), &b.pk, j.off.data(), j.len.data(), j.rc.data(), dst.data() + base,
+                                                                            cap, eoff.data()))
+                                     : DEVT(agc_hip_lz_encode_batch_dev(hip, j.n(), j.gid.data(), b.d_base, j.off.data(), j.len.data(), j.rc.data(), dst.data() + base,
+                                                                        cap, eoff.data()));
+        if (r != AGC_HIP_ECAP)
+            return hip_ok(r, "lz_encode_batch");
+        cap = eoff[j.n()] + eoff[j.n()] / 8 + 4096;
+    }
+}
+
+// The same loop around the collection of an encode that was only launched, ne deltas.  lane < 0: the one the thread that drives
+// the steps began (agc_hip_lz_encode_end, counted as device time); lane >= 0: that device lane's, from the bookkeeping thread --
+// nothing but the lane's own state and dst is touched, and the device must hold as many deltas as the host expects.
+// The lane is the caller's to release.
+bool CAGCCompressor::Impl::collect_lane(int lane, PinnedBytes &dst, uint64_t base, uint64_t first_cap, size_t ne, std::vector<uint64_t> &eoff)
+{
+    eoff.assign(ne + 1, 0);
+    if (lane >= 0) {
+        uint32_t n_dev = 0;
+        if (!hip_ok(agc_hip_lz_encode_pending_on(hip, (uint32_t)lane, &n_dev), "lz_encode_pending"))
+            return false;
+        if (n_dev != ne) {
+            err("internal: the device's encode delivers another number of deltas than the host expects");
+            return false;
+        }
+    }
+    for (uint64_t cap = first_cap;;) {
+        if (!dst.resize(base + cap, base != 0)) {
+            err("out of memory (delta buffer)");
+            return false;
+        }
+        const int r = lane < 0 ? DEVT(agc_hip_lz_encode_end(hip, dst.data() + base, cap, eoff.data()))
+                               : agc_hip_lz_encode_end_on(hip, (uint32_t)lane, dst.data() + base, cap, eoff.data());
+        if (r != AGC_HIP_ECAP)
+            return hip_ok(r, "lz_encode_end");
+        cap = eoff[ne] + eoff[ne] / 8 + 4096;
+    }
+}
+
 // Up-front LZ encode of the window's items whose group already has its reference: group references never change
 // (segment.cpp:41-48), so these deltas stay valid whatever earlier registrations of the window mint.
 bool CAGCCompressor::Impl::spec_encode(BatchState &b)
 {
     finish_spec_fill(b);
     const std::vector<Placed> &placed = placed_buf;
-    double &t0 = b.t0, &dev0 = b.dev0;
     if (b.spec.size() != 2 * seg_buf.size()) {
         b.spec.assign(2 * seg_buf.size(), BatchState::Spec());
         b.spec_bytes = 0;
@@ -988,54 +1006,20 @@ bool CAGCCompressor::Impl::spec_encode(BatchState &b)
             items.push_back(i);
     if (items.empty())
         return true;
+    const EncodeJobs j = encode_jobs(items);
     const size_t ne = items.size();
-    std::vector<uint32_t> gid(ne), len(ne);
-    std::vector<uint64_t> off(ne), eoff(ne + 1, 0);
-    std::vector<uint8_t> rc(ne);
-    uint64_t tot = 0;
-    for (size_t i = 0; i < ne; ++i) {
-        const Placed &pl = placed[items[i]];
-        gid[i] = (uint32_t)pl.gid;
-        off[i] = pl.off;
-        len[i] = pl.len;
-        rc[i] = pl.rc;
-        tot += pl.len;
-        st.enc_text += pl.len;
-        st.enc_ref += groups[pl.gid].ref_size ? groups[pl.gid].ref_size - 1 : 0;
-    }
-    PinnedBytes &enc = enc_buf;
     const uint64_t base = b.spec_bytes; // the deltas are appended to what the window already holds
-    uint64_t cap = std::max<uint64_t>(enc.size() > base ? enc.size() - base : 0, tot / 64 + (1u << 20));
-    for (;;) {
-        if (enc.size() < base + cap)
-            enc.resize(base + cap);
-        int r = b.pk.n_symbols ? DEVT(agc_hip_lz_encode_batch_packed(hip, (uint32_t)ne, gid.data(), &b.pk, off.data(), len.data(), rc.data(), enc.data() + base,
-                                                                      cap, eoff.data()))
-                               : DEVT(agc_hip_lz_encode_batch_dev(hip, (uint32_t)ne, gid.data(), b.d_base, off.data(), len.data(), rc.data(), enc.data() + base, cap,
-                                                                  eoff.data()));
-        if (r == AGC_HIP_ECAP) {
-            cap = eoff[ne] + eoff[ne] / 8 + 4096; // (headroom: the next sample's deltas are a little longer, and a retry runs the kernel again)
-            continue;
-        }
-        if (!hip_ok(r, "lz_encode_batch"))
-            return false;
-        break;
-    }
+    std::vector<uint64_t> eoff;
+    if (!encode_now(b, j, enc_buf, base, std::max<uint64_t>(enc_buf.size() > base ? enc_buf.size() - base : 0, j.tot / 64 + (1u << 20)), eoff))
+        return false;
     for (size_t i = 0; i < ne; ++i) {
         const Placed &pl = placed[items[i]];
-        BatchState::Spec &sp = b.spec[pl.key];
-        sp.valid = true;
-        sp.gid = gid[i];
-        sp.off = pl.off;
-        sp.len = pl.len;
-        sp.rc = pl.rc;
-        sp.enc_off = base + eoff[i];
-        sp.enc_len = (uint32_t)(eoff[i + 1] - eoff[i]);
+        b.spec[pl.key].set((uint32_t)pl.gid, pl.off, pl.len, pl.rc, base + eoff[i], (uint32_t)(eoff[i + 1] - eoff[i]));
     }
     b.spec_bytes = base + eoff[ne];
     st.lz_encoded += ne;
     st.delta_bytes += eoff[ne];
-    stage_end(st.t_encode, st.h_encode, t0, dev0);
+    stage_end(st.t_encode, st.h_encode, b.t0, b.dev0);
     return true;
 }
 
@@ -1054,32 +1038,24 @@ bool CAGCCompressor::Impl::overlap_encode_begin(BatchState &b)
         b.spec_bytes = 0;
     }
     b.flight_keys.clear();
-    b.flight_gid.clear();
-    b.flight_len.clear();
-    b.flight_off.clear();
-    b.flight_rc.clear();
+    b.flight = EncodeJobs();
     for (uint32_t si : b.subset) {
         const Seg &s = segs[si];
         if (!s.front.full || !s.back.full || s.map_gid < (int32_t)NO_RAW_GROUPS)
             continue;
-        const int32_t mg = s.map_gid, *m = &mg;
-        const Group &g = groups[*m];
+        const Group &g = groups[s.map_gid];
         if (!g.exists || g.packed)
             continue;
         b.flight_keys.push_back(2 * si);
-        b.flight_gid.push_back((uint32_t)*m);
-        b.flight_off.push_back(ctgs[s.ctg].off + s.start);
-        b.flight_len.push_back(s.len);
-        b.flight_rc.push_back((uint8_t)s.store_rc);
+        b.flight.add((uint32_t)s.map_gid, ctgs[s.ctg].off + s.start, s.len, s.store_rc);
         st.enc_text += s.len;
         st.enc_ref += g.ref_size ? g.ref_size - 1 : 0;
     }
     if (b.flight_keys.empty())
         return true;
-    if (!hip_ok(b.pk.n_symbols ? DEVT(agc_hip_lz_encode_begin_packed(hip, (uint32_t)b.flight_keys.size(), b.flight_gid.data(), &b.pk, b.flight_off.data(),
-                                                                     b.flight_len.data(), b.flight_rc.data()))
-                               : DEVT(agc_hip_lz_encode_begin_dev(hip, (uint32_t)b.flight_keys.size(), b.flight_gid.data(), b.d_base, b.flight_off.data(),
-                                                                  b.flight_len.data(), b.flight_rc.data())),
+    const EncodeJobs &j = b.flight;
+    if (!hip_ok(b.pk.n_symbols ? DEVT(agc_hip_lz_encode_begin_packed(hip, j.n(), j.gid.data(), &b.pk, j.off.data(), j.len.data(), j.rc.data()))
+                               : DEVT(agc_hip_lz_encode_begin_dev(hip, j.n(), j.gid.data(), b.d_base, j.off.data(), j.len.data(), j.rc.data())),
                 "lz_encode_begin"))
         return false;
     b.enc_in_flight = true;
@@ -1090,38 +1066,15 @@ bool CAGCCompressor::Impl::overlap_encode_end(BatchState &b)
 {
     finish_spec_fill(b);
     const size_t ne = b.flight_keys.size();
-    std::vector<uint64_t> eoff(ne + 1, 0);
-    uint64_t tot = 0;
-    for (uint32_t l : b.flight_len)
-        tot += l;
-    PinnedBytes &enc = enc_buf;
+    const EncodeJobs &j = b.flight;
     const uint64_t base = b.spec_bytes;
-    uint64_t cap = std::max<uint64_t>(enc.size() > base ? enc.size() - base : 0, tot / 64 + (1u << 20));
-    for (;;) {
-        if (!enc.resize(base + cap)) {
-            err("out of memory (delta buffer)");
-            return false;
-        }
-        int r = DEVT(agc_hip_lz_encode_end(hip, enc.data() + base, cap, eoff.data()));
-        if (r == AGC_HIP_ECAP) {
-            cap = eoff[ne] + 64 + eoff[ne] / 8; // (headroom: the next samples' deltas are about as long)
-            continue;
-        }
-        b.enc_in_flight = false;
-        if (!hip_ok(r, "lz_encode_end"))
-            return false;
-        break;
-    }
-    for (size_t i = 0; i < ne; ++i) {
-        BatchState::Spec &sp = b.spec[b.flight_keys[i]];
-        sp.valid = true;
-        sp.gid = b.flight_gid[i];
-        sp.off = b.flight_off[i];
-        sp.len = b.flight_len[i];
-        sp.rc = b.flight_rc[i] != 0;
-        sp.enc_off = base + eoff[i];
-        sp.enc_len = (uint32_t)(eoff[i + 1] - eoff[i]);
-    }
+    std::vector<uint64_t> eoff;
+    const bool ok = collect_lane(-1, enc_buf, base, std::max<uint64_t>(enc_buf.size() > base ? enc_buf.size() - base : 0, j.tot / 64 + (1u << 20)), ne, eoff);
+    b.enc_in_flight = false;
+    if (!ok)
+        return false;
+    for (size_t i = 0; i < ne; ++i)
+        b.spec[b.flight_keys[i]].set(j.gid[i], j.off[i], j.len[i], j.rc[i] != 0, base + eoff[i], (uint32_t)(eoff[i + 1] - eoff[i]));
     b.spec_bytes = base + eoff[ne];
     st.lz_encoded += ne;
     st.delta_bytes += eoff[ne];
@@ -1172,7 +1125,69 @@ void CAGCCompressor::Impl::lap(BatchState &b, const char *what)
     b.lap_t = now();
 }
 
-// compress_contig for every contig of the window: splitter hits from the GPU, adaptive-mode re-scan, segments
+// The window's table of contig offsets (n_ctg + 1 entries; the contigs of a window lie one behind the other in HBM); its symbols
+// go to the statistics
+bool CAGCCompressor::Impl::window_offsets(const BatchState &b, std::vector<uint64_t> &ctg_off)
+{
+    const std::vector<Contig> &ctgs = *b.ctgs;
+    ctg_off.assign((size_t)b.n_ctg + 1, 0);
+    for (uint32_t i = 0; i < b.n_ctg; ++i) {
+        ctg_off[i] = ctgs[i].off;
+        st.bases += ctgs[i].len;
+        if (i + 1 < b.n_ctg && ctgs[i].off + ctgs[i].len != ctgs[i + 1].off) {
+            err("internal: contigs of a batch must be contiguous in HBM");
+            return false;
+        }
+    }
+    if (b.n_ctg)
+        ctg_off[b.n_ctg] = ctgs.back().off + ctgs.back().len;
+    return true;
+}
+
+// ... and taken back for the contigs from `from_ctg` on: whoever scans them next counts them again
+void CAGCCompressor::Impl::uncount_bases(BatchState &b, uint32_t from_ctg)
+{
+    for (uint32_t i = from_ctg; i < b.n_ctg; ++i)
+        st.bases -= (*b.ctgs)[i].len;
+}
+
+// a sample prepared ahead of its turn would have to extend the splitter set, which is not its to extend yet: it only says so and
+// is prepared again at its turn
+void CAGCCompressor::Impl::wait_for_turn(BatchState &b)
+{
+    b.needs_turn = true;
+    uncount_bases(b, 0);
+}
+
+// Adaptive mode: the contigs `need` -- without any splitter, long enough to carry one -- look for new ones (agc_compressor.cpp:
+// 2038-2044, 2054-2081): their symbols come to the host unless host_data has them, find_new_splitters runs on the pool.
+bool CAGCCompressor::Impl::mine_contigs(BatchState &b, const std::vector<uint32_t> &need, std::vector<std::vector<uint64_t>> &found)
+{
+    const std::vector<Contig> &ctgs = *b.ctgs;
+    const std::vector<bytes_t> *host_data = b.host_data;
+    found.assign(need.size(), std::vector<uint64_t>());
+    std::vector<bytes_t> fetched_ctg(need.size());
+    if (!need.empty() && !host_data) {
+        std::vector<uint64_t> off(need.size()), ooff(need.size() + 1);
+        std::vector<uint32_t> len(need.size());
+        uint64_t tot = 0;
+        for (size_t i = 0; i < need.size(); ++i) {
+            off[i] = ctgs[need[i]].off;
+            len[i] = (uint32_t)ctgs[need[i]].len;
+            tot += len[i];
+        }
+        bytes_t buf(tot);
+        if (!hip_ok(b.pk.n_symbols ? DEVT(agc_hip_fetch_slices_packed(hip, (uint32_t)need.size(), &b.pk, off.data(), len.data(), nullptr, buf.data(), tot, ooff.data()))
+                                   : DEVT(agc_hip_fetch_slices_dev(hip, (uint32_t)need.size(), b.d_base, off.data(), len.data(), nullptr, buf.data(), tot, ooff.data())),
+                    "fetch_slices"))
+            return false;
+        for (size_t i = 0; i < need.size(); ++i)
+            fetched_ctg[i].assign(buf.begin() + ooff[i], buf.begin() + ooff[i + 1]);
+    }
+    pool->parallel_for(need.size(), [&](size_t i, unsigned) { find_new_splitters(host_data ? (*host_data)[need[i]] : fetched_ctg[i], found[i]); });
+    return true;
+}
+
 // the device delivers segments, not hits: scan (or its prefetched result), reset rule, cut, keys and their look-up in the group
 // table all run there (agc_hip_segments_packed), and the encode of every segment whose group is known is launched from there
 // Every mode takes it (round 5): windows of several registrations and -c (the keys the device looked up are those of the window's
@@ -1191,16 +1206,9 @@ int CAGCCompressor::Impl::stage_scan_dev(BatchState &b)
     const std::vector<Contig> &ctgs = *b.ctgs;
     const uint32_t n_ctg = b.n_ctg;
     double &t0 = b.t0, &dev0 = b.dev0;
-    std::vector<uint64_t> ctg_off(n_ctg + 1, 0);
-    for (uint32_t i = 0; i < n_ctg; ++i) {
-        ctg_off[i] = ctgs[i].off;
-        st.bases += ctgs[i].len;
-        if (i + 1 < n_ctg && ctgs[i].off + ctgs[i].len != ctgs[i + 1].off) {
-            err("internal: contigs of a batch must be contiguous in HBM");
-            return 0;
-        }
-    }
-    ctg_off[n_ctg] = ctgs.back().off + ctgs.back().len;
+    std::vector<uint64_t> ctg_off;
+    if (!window_offsets(b, ctg_off))
+        return 0;
     // the groups minted since the last sample go to the device's table first
     if (!hip_ok(DEVT(map_segments.sync_device(hip)), "group_map"))
         return 0;
@@ -1252,126 +1260,21 @@ int CAGCCompressor::Impl::stage_scan_dev(BatchState &b)
     stage_end(st.t_scan, st.h_scan, t0, dev0);
     t0 = now();
     lap(b, "scan + segments (device)");
-    // the device's records -> the host's (the pool: 50 k records of a human sample)
-    const agc_hip_segment *dsegs = (const agc_hip_segment *)dev_seg_buf.data();
-    std::vector<Seg> &segs = seg_buf;
-    segs.resize(n_segs);
     // the encode of the segments whose group the table knew is launched on the device's second lane when its deltas can be
     // collected beside the next sample (bookkeeping thread); otherwise the commit encodes as before
     // (... and when the sample is large enough to fill the GPU with one wavefront per segment: the few dozen segments of a bacterial
     // genome are encoded from the host's descriptors at commit time instead, where the library parses them in chunks)
     const bool enc = sw.async_encode && book_can_async(1) && b.base_owned && ctgs.back().sample_idx == 0 && n_segs >= sw.dev_encode_min;
     std::vector<uint8_t> is_known(enc ? n_segs : 0, 0);
-    {
-        const size_t n_chunks = n_segs >= sw.par_min ? std::min<size_t>(std::max<size_t>(n_segs / 2048, 2), (size_t)pool->size() * 4) : 1;
-        auto conv = [&](size_t ci, unsigned) {
-            for (size_t i = n_segs * ci / n_chunks; i < n_segs * (ci + 1) / n_chunks; ++i) {
-                const agc_hip_segment &d = dsegs[i];
-                Seg &s = segs[i];
-                s.ctg = d.ctg;
-                s.start = d.start;
-                s.len = d.len;
-                s.front.dir = d.front_dir;
-                s.front.rc = d.front_rc;
-                s.front.full = d.front_full != 0;
-                s.back.dir = d.back_dir;
-                s.back.rc = d.back_rc;
-                s.back.full = d.back_full != 0;
-                s.dev_gid = d.front_full && d.back_full ? d.map_gid : -2;
-                // (the rule of known_flag_kernel: two splitters, a group of its own, its reference in HBM)
-                if (enc && d.front_full && d.back_full && d.map_gid >= (int32_t)NO_RAW_GROUPS && (size_t)d.map_gid < groups.size() &&
-                    groups[(uint32_t)d.map_gid].exists && !groups[(uint32_t)d.map_gid].packed)
-                    is_known[i] = 1;
-            }
-        };
-        if (n_chunks > 1)
-            pool->parallel_for(n_chunks, conv);
-        else
-            conv(0, 0);
-    }
+    dev_segments_to_host(n_segs, enc, is_known);
     lap(b, "segments -> host records");
-    // ---- adaptive mode: contigs without any splitter look for new ones (agc_compressor.cpp:2038-2044, 2054-2081).  When they
-    // find none -- nearly always: a sample that resembles the collection has splitters in every contig -- the device's segments
-    // stand; when the set has to grow the window goes the host's way (only those contigs take the second scan's hits,
-    // :1187-1237), with what was mined here
     if (adaptive) {
-        std::vector<uint32_t> need;
-        for (size_t i = 0; i < n_segs; ++i)
-            if ((i == 0 || dsegs[i - 1].ctg != dsegs[i].ctg) && !dsegs[i].back_full && ctgs[dsegs[i].ctg].len >= segment_size)
-                need.push_back(dsegs[i].ctg);
-        if (!need.empty()) {
-            const std::vector<bytes_t> *host_data = b.host_data;
-            std::vector<bytes_t> fetched_ctg(need.size());
-            if (!host_data) {
-                std::vector<uint64_t> off(need.size()), ooff(need.size() + 1);
-                std::vector<uint32_t> len(need.size());
-                uint64_t tot = 0;
-                for (size_t i = 0; i < need.size(); ++i) {
-                    off[i] = ctgs[need[i]].off;
-                    len[i] = (uint32_t)ctgs[need[i]].len;
-                    tot += len[i];
-                }
-                bytes_t buf(tot);
-                if (!hip_ok(DEVT(agc_hip_fetch_slices_packed(hip, (uint32_t)need.size(), &b.pk, off.data(), len.data(), nullptr, buf.data(), tot, ooff.data())),
-                            "fetch_slices"))
-                    return 0;
-                for (size_t i = 0; i < need.size(); ++i)
-                    fetched_ctg[i].assign(buf.begin() + ooff[i], buf.begin() + ooff[i + 1]);
-            }
-            std::vector<std::vector<uint64_t>> found(need.size());
-            pool->parallel_for(need.size(), [&](size_t i, unsigned) { find_new_splitters(host_data ? (*host_data)[need[i]] : fetched_ctg[i], found[i]); });
-            // the first registration of the window that has to extend the set.  A window of several registrations (round 5: adaptive
-            // mode speculates too) is valid as far as the set it was scanned with is: the registrations in front of that one
-            // stand, the one itself and everything behind it come again -- it as the first of its window, where the set is its
-            // to extend (agc_compressor.cpp:1187-1237: new splitters take effect for the contigs that come after)
-            uint32_t first_bad = ~0u;
-            for (size_t i = 0; i < need.size(); ++i)
-                if (!found[i].empty())
-                    first_bad = std::min(first_bad, ctgs[need[i]].sample_idx);
-            if (first_bad != ~0u) {
-                const uint32_t keep = first_bad == 0 ? 1u : first_bad; // registrations that stay in this window
-                if (ctgs.back().sample_idx >= keep) {
-                    uint32_t nc = 0;
-                    while (nc < n_ctg && ctgs[nc].sample_idx < keep)
-                        ++nc;
-                    for (uint32_t i = nc; i < n_ctg; ++i)
-                        st.bases -= ctgs[i].len;
-                    size_t ns = 0;
-                    while (ns < n_segs && dsegs[ns].ctg < nc)
-                        ++ns;
-                    b.ctgs->resize(nc);
-                    b.n_ctg = nc;
-                    segs.resize(ns);
-                    ++st.windows_cut;
-                    if (first_bad != 0) { // nothing new in what is left: the device's segments stand
-                        lap(b, "window cut at the registration that brings new splitters");
-                        b.dev_enc_n = 0;
-                        return 1;
-                    }
-                }
-                // the window's first registration extends the set (the window is that registration alone by now)
-                for (uint32_t i = 0; i < b.n_ctg; ++i)
-                    st.bases -= (*b.ctgs)[i].len; // (counted again by whoever scans the window next)
-                b.dev_keys = false;
-                if (b.no_new_splitters) { // prepared ahead of its turn: the set is not this sample's to extend yet
-                    b.needs_turn = true;
-                    return 1;
-                }
-                std::vector<uint32_t> need0;
-                std::vector<std::vector<uint64_t>> found0;
-                for (size_t i = 0; i < need.size(); ++i)
-                    if (need[i] < b.n_ctg) {
-                        need0.push_back(need[i]);
-                        found0.emplace_back(std::move(found[i]));
-                    }
-                b.mined_valid = true;
-                b.mined_need.swap(need0);
-                b.mined_found.swap(found0);
-                return 2;
-            }
-        }
-        lap(b, "contigs without a splitter: nothing new");
+        const int r = mine_dev_window(b, n_segs);
+        if (r >= 0)
+            return r;
     }
+    const agc_hip_segment *dsegs = (const agc_hip_segment *)dev_seg_buf.data();
+    std::vector<Seg> &segs = seg_buf;
     uint32_t n_enc = 0;
     if (enc) {
         // The launch first: it needs nothing from the host but the count (the device made the descriptors), and the table of
@@ -1414,15 +1317,7 @@ int CAGCCompressor::Impl::stage_scan_dev(BatchState &b)
                 if (!known[i])
                     continue;
                 const agc_hip_segment &d = dsegs[i];
-                BatchState::Spec &sp = b.spec[2 * i];
-                sp.valid = true;
-                sp.gid = (uint32_t)d.map_gid;
-                sp.off = ctgs[d.ctg].off + d.start;
-                sp.len = d.len;
-                sp.rc = d.store_rc != 0;
-                sp.enc_off = 0;
-                sp.enc_len = 0;
-                sp.pending = (int32_t)k_enc++;
+                b.spec[2 * i].set((uint32_t)d.map_gid, ctgs[d.ctg].off + d.start, d.len, d.store_rc != 0, 0, 0, (int32_t)k_enc++);
                 text += d.len;
                 ref += groups[(uint32_t)d.map_gid].ref_size ? groups[(uint32_t)d.map_gid].ref_size - 1 : 0;
             }
@@ -1441,6 +1336,107 @@ int CAGCCompressor::Impl::stage_scan_dev(BatchState &b)
     return 1;
 }
 
+// the device's records -> the host's (the pool: 50 k records of a human sample); enc: is_known[i] says whether segment i is one the
+// device launches the encode of
+void CAGCCompressor::Impl::dev_segments_to_host(size_t n_segs, bool enc, std::vector<uint8_t> &is_known)
+{
+    const agc_hip_segment *dsegs = (const agc_hip_segment *)dev_seg_buf.data();
+    std::vector<Seg> &segs = seg_buf;
+    segs.resize(n_segs);
+    const size_t n_chunks = n_segs >= sw.par_min ? std::min<size_t>(std::max<size_t>(n_segs / 2048, 2), (size_t)pool->size() * 4) : 1;
+    auto conv = [&](size_t ci, unsigned) {
+        for (size_t i = n_segs * ci / n_chunks; i < n_segs * (ci + 1) / n_chunks; ++i) {
+            const agc_hip_segment &d = dsegs[i];
+            Seg &s = segs[i];
+            s.ctg = d.ctg;
+            s.start = d.start;
+            s.len = d.len;
+            s.front.dir = d.front_dir;
+            s.front.rc = d.front_rc;
+            s.front.full = d.front_full != 0;
+            s.back.dir = d.back_dir;
+            s.back.rc = d.back_rc;
+            s.back.full = d.back_full != 0;
+            s.dev_gid = d.front_full && d.back_full ? d.map_gid : -2;
+            // (the rule of known_flag_kernel: two splitters, a group of its own, its reference in HBM)
+            if (enc && d.front_full && d.back_full && d.map_gid >= (int32_t)NO_RAW_GROUPS && (size_t)d.map_gid < groups.size() &&
+                groups[(uint32_t)d.map_gid].exists && !groups[(uint32_t)d.map_gid].packed)
+                is_known[i] = 1;
+        }
+    };
+    if (n_chunks > 1)
+        pool->parallel_for(n_chunks, conv);
+    else
+        conv(0, 0);
+}
+
+// ---- adaptive mode: contigs without any splitter look for new ones (agc_compressor.cpp:2038-2044, 2054-2081).  When they
+// find none -- nearly always: a sample that resembles the collection has splitters in every contig -- the device's segments
+// stand; when the set has to grow the window goes the host's way (only those contigs take the second scan's hits,
+// :1187-1237), with what was mined here
+// -> -1 nothing new, the stage goes on; else what stage_scan_dev returns
+int CAGCCompressor::Impl::mine_dev_window(BatchState &b, size_t n_segs)
+{
+    const std::vector<Contig> &ctgs = *b.ctgs;
+    const agc_hip_segment *dsegs = (const agc_hip_segment *)dev_seg_buf.data();
+    std::vector<uint32_t> need;
+    for (size_t i = 0; i < n_segs; ++i)
+        if ((i == 0 || dsegs[i - 1].ctg != dsegs[i].ctg) && !dsegs[i].back_full && ctgs[dsegs[i].ctg].len >= segment_size)
+            need.push_back(dsegs[i].ctg);
+    std::vector<std::vector<uint64_t>> found;
+    if (!mine_contigs(b, need, found))
+        return 0;
+    // the first registration of the window that has to extend the set.  A window of several registrations (round 5: adaptive
+    // mode speculates too) is valid as far as the set it was scanned with is: the registrations in front of that one
+    // stand, the one itself and everything behind it come again -- it as the first of its window, where the set is its
+    // to extend (agc_compressor.cpp:1187-1237: new splitters take effect for the contigs that come after)
+    uint32_t first_bad = ~0u;
+    for (size_t i = 0; i < need.size(); ++i)
+        if (!found[i].empty())
+            first_bad = std::min(first_bad, ctgs[need[i]].sample_idx);
+    if (first_bad != ~0u) {
+        const uint32_t keep = first_bad == 0 ? 1u : first_bad; // registrations that stay in this window
+        if (ctgs.back().sample_idx >= keep) {
+            uint32_t nc = 0;
+            while (nc < b.n_ctg && ctgs[nc].sample_idx < keep)
+                ++nc;
+            uncount_bases(b, nc);
+            size_t ns = 0;
+            while (ns < n_segs && dsegs[ns].ctg < nc)
+                ++ns;
+            b.ctgs->resize(nc);
+            b.n_ctg = nc;
+            seg_buf.resize(ns);
+            ++st.windows_cut;
+            if (first_bad != 0) { // nothing new in what is left: the device's segments stand
+                lap(b, "window cut at the registration that brings new splitters");
+                b.dev_enc_n = 0;
+                return 1;
+            }
+        }
+        // the window's first registration extends the set (the window is that registration alone by now)
+        b.dev_keys = false;
+        if (b.no_new_splitters) {
+            wait_for_turn(b);
+            return 1;
+        }
+        uncount_bases(b, 0); // (the host's scan counts them again)
+        std::vector<uint32_t> need0;
+        std::vector<std::vector<uint64_t>> found0;
+        for (size_t i = 0; i < need.size(); ++i)
+            if (need[i] < b.n_ctg) {
+                need0.push_back(need[i]);
+                found0.emplace_back(std::move(found[i]));
+            }
+        b.mined_valid = true;
+        b.mined_need.swap(need0);
+        b.mined_found.swap(found0);
+        return 2;
+    }
+    lap(b, "contigs without a splitter: nothing new");
+    return -1;
+}
+
 // The launch of the whole-sample encode from the descriptors the device made (stage_scan_dev), queued at once: beside the estimates
 // and the cost vectors.  (Behind the estimates, or behind the whole classification -- beside the announced scan and the FASTA
 // conversion --, was measured in round 6: median step 13.7-15.5 ms against 12.6-13.2, profiles/EXPERIMENTS.md.)
@@ -1450,35 +1446,31 @@ bool CAGCCompressor::Impl::launch_known_encode(BatchState &b, bool launched_alre
         return true;
     b.known_launch_due = false;
     const uint32_t n_enc = b.dev_enc_n;
-    {
-        {
-            if (!launched_already) { // (launched_already: inside agc_hip_segments_packed, the lane taken before that call)
-                lane2_acquire(); // (the previous sample's deltas have been collected: they were while the table came over)
-                lap(b, "second lane free");
-                if (!hip_ok(DEVT(agc_hip_segments_encode_known(hip)), "segments_encode_known")) {
-                    lane2_release();
-                    b.dev_enc_n = 0;
-                    return false;
-                }
-            }
-            st.lz_encoded += n_enc;
-            // The deltas are collected as soon as the kernel is done -- an early task of the bookkeeping thread, queued now -- when
-            // it is certain already that the registration's books are that thread's too (stage_store_finish: hand_over).  The lane
-            // is then free long before the next sample's launch asks for it (it used to be released by the registration's own
-            // task, a whole step later: 0.9 ms of "second lane free" per human-size sample) and that task starts with its deltas
-            // on the host.  enc_buf is nobody's until the hand-over swaps the buffer sets (bulk mode: spec_bytes == 0).
-            if (sw.early_collect && dist_world == 1 && book_can_async(1) && b.spec_bytes == 0) {
-                const uint64_t text = b.known_text;
-                std::unique_ptr<BookTask> t(new BookTask());
-                t->early_only = true;
-                t->enc_n = n_enc;
-                t->enc_text = text;
-                if (!enc_buf.ctx)
-                    enc_buf.ctx = hip;
-                t->enc_dst = &enc_buf;
-                b.early_seq = book_submit(std::move(t));
-            }
+    if (!launched_already) { // (launched_already: inside agc_hip_segments_packed, the lane taken before that call)
+        lane2_acquire(); // (the previous sample's deltas have been collected: they were while the table came over)
+        lap(b, "second lane free");
+        if (!hip_ok(DEVT(agc_hip_segments_encode_known(hip)), "segments_encode_known")) {
+            lane2_release();
+            b.dev_enc_n = 0;
+            return false;
         }
+    }
+    st.lz_encoded += n_enc;
+    // The deltas are collected as soon as the kernel is done -- an early task of the bookkeeping thread, queued now -- when
+    // it is certain already that the registration's books are that thread's too (stage_store_finish: hand_over).  The lane
+    // is then free long before the next sample's launch asks for it (it used to be released by the registration's own
+    // task, a whole step later: 0.9 ms of "second lane free" per human-size sample) and that task starts with its deltas
+    // on the host.  enc_buf is nobody's until the hand-over swaps the buffer sets (bulk mode: spec_bytes == 0).
+    if (sw.early_collect && dist_world == 1 && book_can_async(1) && b.spec_bytes == 0) {
+        const uint64_t text = b.known_text;
+        std::unique_ptr<BookTask> t(new BookTask());
+        t->early_only = true;
+        t->enc_n = n_enc;
+        t->enc_text = text;
+        if (!enc_buf.ctx)
+            enc_buf.ctx = hip;
+        t->enc_dst = &enc_buf;
+        b.early_seq = book_submit(std::move(t));
     }
     lap(b, "encode of the known segments launched");
     return true;
@@ -1491,212 +1483,223 @@ bool CAGCCompressor::Impl::stage_scan(BatchState &b)
         if (r != 2)
             return r == 1;
     }
-    const std::vector<Contig> &ctgs = *b.ctgs;
-    const uint8_t *d_base = b.d_base;
-    const uint32_t n_ctg = b.n_ctg;
-    double &t0 = b.t0, &dev0 = b.dev0;
-    auto LAP = [&](const char *what) { lap(b, what); };
-    (void)ctgs; (void)d_base; (void)n_ctg; (void)t0; (void)dev0; (void)LAP;
-    const std::vector<bytes_t> *host_data = b.host_data;
-    std::vector<uint64_t> &new_splitters_added = b.new_splitters_added;
+    return stage_scan_host(b);
+}
+
+// the hits come to the host: cut and key look-up there.  Windows the device's segments are not for (use_dev_segments), and the
+// window whose first registration extends the splitter set in adaptive mode
+bool CAGCCompressor::Impl::stage_scan_host(BatchState &b)
+{
     // ---- stage 1a: splitter scan on the GPU (compress_contig's loop) ----
-    std::vector<uint64_t> ctg_off(n_ctg + 1, 0);
-    for (uint32_t i = 0; i < n_ctg; ++i) {
-        ctg_off[i] = ctgs[i].off;
-        st.bases += ctgs[i].len;
-    }
-    if (n_ctg)
-        ctg_off[n_ctg] = ctgs.back().off + ctgs.back().len;
-    for (uint32_t i = 0; i + 1 < n_ctg; ++i)
-        if (ctgs[i].off + ctgs[i].len != ctgs[i + 1].off) {
-            err("internal: contigs of a batch must be contiguous in HBM");
-            return false;
+    std::vector<uint64_t> ctg_off;
+    if (!window_offsets(b, ctg_off))
+        return false;
+    uint64_t n_hits = 0;
+    if (b.n_ctg && scan_batch(ctg_off, b.n_ctg, b.d_base, scan_ctg, scan_pos, scan_dir, scan_rc, n_hits) != AGC_HIP_OK)
+        return false;
+    if (adaptive && b.n_ctg && !extend_splitters(b, ctg_off, n_hits))
+        return false;
+    if (b.needs_turn)
+        return true;
+    stage_end(st.t_scan, st.h_scan, b.t0, b.dev0);
+    b.t0 = now();
+    lap(b, "scan");
+    cut_segments(b, n_hits);
+    return true;
+}
+
+// ---- adaptive mode: contigs without any splitter look for new ones, the set is extended and
+// those contigs are scanned again (agc_compressor.cpp:2038-2044, 2054-2081, 1187-1237) ----
+bool CAGCCompressor::Impl::extend_splitters(BatchState &b, const std::vector<uint64_t> &ctg_off, uint64_t &n_hits)
+{
+    const std::vector<Contig> &ctgs = *b.ctgs;
+    const uint32_t n_ctg = b.n_ctg;
+    std::vector<uint8_t> has_hit(n_ctg, 0);
+    for (uint64_t h = 0; h < n_hits; ++h)
+        has_hit[scan_ctg[h]] = 1;
+    // contigs without a hit that are long enough to carry a splitter
+    std::vector<uint32_t> need;
+    bool deferred = false;
+    for (uint32_t c = 0; c < n_ctg; ++c)
+        if (!has_hit[c]) {
+            deferred = true;
+            if (ctgs[c].len >= segment_size)
+                need.push_back(c);
         }
+    if (!deferred)
+        return true;
+    std::vector<std::vector<uint64_t>> found;
+    if (b.mined_valid && b.mined_need == need) // (the device path looked already: stage_scan_dev)
+        found.swap(b.mined_found);
+    else if (!mine_contigs(b, need, found))
+        return false;
+    b.mined_valid = false;
+    std::vector<uint64_t> add;
+    for (auto &f : found)
+        add.insert(add.end(), f.begin(), f.end());
+    if (add.empty())
+        return true;
+    if (b.no_new_splitters) {
+        wait_for_turn(b);
+        return true;
+    }
+    ++spl_version;
+    splitters.insert(splitters.end(), add.begin(), add.end());
+    std::sort(splitters.begin(), splitters.end());
+    splitters.erase(std::unique(splitters.begin(), splitters.end()), splitters.end());
+    if (!hip_ok(DEVT(agc_hip_splitters_insert(hip, add.data(), add.size())), "splitters_insert"))
+        return false;
+    b.new_splitters_added = add;
+    // second scan with the extended set; only the deferred contigs take its hits
+    std::vector<uint32_t> c2;
+    std::vector<uint64_t> p2, d2, r2;
+    uint64_t n2 = 0;
+    if (scan_batch(ctg_off, n_ctg, b.d_base, c2, p2, d2, r2, n2) != AGC_HIP_OK)
+        return false;
+    merge_rescan_hits(has_hit, n_hits, c2, p2, d2, r2, n2);
+    return true;
+}
+
+// the hit list after a second scan: per contig, the first scan's hits where it had any, the second scan's otherwise
+void CAGCCompressor::Impl::merge_rescan_hits(const std::vector<uint8_t> &has_hit, uint64_t &n_hits, const std::vector<uint32_t> &c2,
+                                             const std::vector<uint64_t> &p2, const std::vector<uint64_t> &d2, const std::vector<uint64_t> &r2, uint64_t n2)
+{
     std::vector<uint32_t> &h_ctg = scan_ctg;
     std::vector<uint64_t> &h_pos = scan_pos, &h_dir = scan_dir, &h_rc = scan_rc;
-    uint64_t n_hits = 0;
-    if (n_ctg && scan_batch(ctg_off, n_ctg, d_base, h_ctg, h_pos, h_dir, h_rc, n_hits) != AGC_HIP_OK)
-        return false;
-
-    // ---- adaptive mode: contigs without any splitter look for new ones, the set is extended and
-    // those contigs are scanned again (agc_compressor.cpp:2038-2044, 2054-2081, 1187-1237) ----
-    if (adaptive && n_ctg) {
-        std::vector<uint8_t> has_hit(n_ctg, 0);
-        for (uint64_t h = 0; h < n_hits; ++h)
-            has_hit[h_ctg[h]] = 1;
-        std::vector<uint32_t> deferred;
-        for (uint32_t c = 0; c < n_ctg; ++c)
-            if (!has_hit[c])
-                deferred.push_back(c);
-        if (!deferred.empty()) {
-            // contigs long enough to carry a splitter: their symbols are needed on the host
-            std::vector<uint32_t> need;
-            for (uint32_t c : deferred)
-                if (ctgs[c].len >= segment_size)
-                    need.push_back(c);
-            std::vector<bytes_t> fetched_ctg(need.size());
-            if (!need.empty() && !host_data && !(b.mined_valid && b.mined_need == need)) {
-                std::vector<uint64_t> off(need.size()), ooff(need.size() + 1);
-                std::vector<uint32_t> len(need.size());
-                uint64_t tot = 0;
-                for (size_t i = 0; i < need.size(); ++i) {
-                    off[i] = ctgs[need[i]].off;
-                    len[i] = (uint32_t)ctgs[need[i]].len;
-                    tot += len[i];
-                }
-                bytes_t buf(tot);
-                if (!hip_ok(b.pk.n_symbols ? DEVT(agc_hip_fetch_slices_packed(hip, (uint32_t)need.size(), &b.pk, off.data(), len.data(), nullptr, buf.data(), tot, ooff.data()))
-                                           : DEVT(agc_hip_fetch_slices_dev(hip, (uint32_t)need.size(), d_base, off.data(), len.data(), nullptr, buf.data(), tot, ooff.data())),
-                            "fetch_slices"))
-                    return false;
-                for (size_t i = 0; i < need.size(); ++i)
-                    fetched_ctg[i].assign(buf.begin() + ooff[i], buf.begin() + ooff[i + 1]);
+    const uint32_t n_ctg = (uint32_t)has_hit.size();
+    std::vector<uint32_t> mc;
+    std::vector<uint64_t> mp, md, mr;
+    uint64_t a = 0, b = 0;
+    for (uint32_t c = 0; c < n_ctg; ++c) {
+        while (a < n_hits && h_ctg[a] < c)
+            ++a;
+        while (b < n2 && c2[b] < c)
+            ++b;
+        if (has_hit[c])
+            for (; a < n_hits && h_ctg[a] == c; ++a) {
+                mc.push_back(c);
+                mp.push_back(h_pos[a]);
+                md.push_back(h_dir[a]);
+                mr.push_back(h_rc[a]);
             }
-            std::vector<std::vector<uint64_t>> found(need.size());
-            if (b.mined_valid && b.mined_need == need) // (the device path looked already: stage_scan_dev)
-                found.swap(b.mined_found);
-            else
-                pool->parallel_for(need.size(), [&](size_t i, unsigned) {
-                    find_new_splitters(host_data ? (*host_data)[need[i]] : fetched_ctg[i], found[i]);
-                });
-            b.mined_valid = false;
-            size_t n_new = 0;
-            for (auto &f : found)
-                n_new += f.size();
-            if (n_new && b.no_new_splitters) {
-                // prepared ahead of its turn: the set is not this sample's to extend yet -- the sample is prepared again at its turn
-                b.needs_turn = true;
-                for (uint32_t i = 0; i < n_ctg; ++i)
-                    st.bases -= ctgs[i].len;
-                return true;
-            }
-            if (n_new) {
-                ++spl_version;
-                std::vector<uint64_t> add;
-                for (auto &f : found)
-                    add.insert(add.end(), f.begin(), f.end());
-                splitters.insert(splitters.end(), add.begin(), add.end());
-                std::sort(splitters.begin(), splitters.end());
-                splitters.erase(std::unique(splitters.begin(), splitters.end()), splitters.end());
-                if (!hip_ok(DEVT(agc_hip_splitters_insert(hip, add.data(), add.size())), "splitters_insert"))
-                    return false;
-                new_splitters_added = add;
-                // second scan with the extended set; only the deferred contigs take its hits
-                std::vector<uint32_t> c2;
-                std::vector<uint64_t> p2, d2, r2;
-                uint64_t n2 = 0;
-                if (scan_batch(ctg_off, n_ctg, d_base, c2, p2, d2, r2, n2) != AGC_HIP_OK)
-                    return false;
-                std::vector<uint32_t> mc;
-                std::vector<uint64_t> mp, md, mr;
-                uint64_t a = 0, b = 0;
-                for (uint32_t c = 0; c < n_ctg; ++c) {
-                    while (a < n_hits && h_ctg[a] < c)
-                        ++a;
-                    while (b < n2 && c2[b] < c)
-                        ++b;
-                    if (has_hit[c])
-                        for (; a < n_hits && h_ctg[a] == c; ++a) {
-                            mc.push_back(c);
-                            mp.push_back(h_pos[a]);
-                            md.push_back(h_dir[a]);
-                            mr.push_back(h_rc[a]);
-                        }
-                    else
-                        for (; b < n2 && c2[b] == c; ++b) {
-                            mc.push_back(c);
-                            mp.push_back(p2[b]);
-                            md.push_back(d2[b]);
-                            mr.push_back(r2[b]);
-                        }
-                }
-                h_ctg.swap(mc);
-                h_pos.swap(mp);
-                h_dir.swap(md);
-                h_rc.swap(mr);
-                n_hits = h_ctg.size();
-            }
-        }
-    }
-    stage_end(st.t_scan, st.h_scan, t0, dev0);
-    t0 = now();
-
-    LAP("scan");
-    // ---- stage 1b: cut into segments (agc_compressor.cpp:2018-2048) ----
-    // The segment records are 208 bytes and a human sample has 50 k of them: they are laid out by a prefix sum over the contigs
-    // and filled by the pool; only the fields the cut defines are written here -- classification (stage_classify) sets every
-    // field it reads before it reads it, so records left over from the previous window need no clearing.
-    std::vector<Seg> &segs = seg_buf;
-    {
-        std::vector<uint64_t> h_begin((size_t)n_ctg + 1, 0), s_begin((size_t)n_ctg + 1, 0);
-        {
-            uint64_t h = 0;
-            for (uint32_t c = 0; c < n_ctg; ++c) {
-                h_begin[c] = h;
-                while (h < n_hits && h_ctg[h] == c)
-                    ++h;
-                const uint64_t nh = h - h_begin[c];
-                const uint64_t last_split = nh ? h_pos[h - 1] + 1 - k : 0;
-                s_begin[c + 1] = s_begin[c] + nh + (last_split < ctgs[c].len ? 1 : 0);
-            }
-            h_begin[n_ctg] = h;
-        }
-        segs.resize(s_begin[n_ctg]); // (grows or shrinks by the difference to the previous window only)
-        LAP("cut_reserve");
-        const size_t n_chunks = std::min<size_t>(n_ctg, std::max<size_t>(1, (size_t)pool->size() * 4));
-        auto fill = [&](size_t ci, unsigned) {
-            for (uint32_t c = (uint32_t)((uint64_t)n_ctg * ci / n_chunks); c < (uint32_t)((uint64_t)n_ctg * (ci + 1) / n_chunks); ++c) {
-                uint64_t split_pos = 0;
-                Kmer split_kmer;
-                Seg *out = segs.data() + s_begin[c];
-                for (uint64_t h = h_begin[c]; h < h_begin[c + 1]; ++h) {
-                    Seg &s = *out++;
-                    s.ctg = c;
-                    s.start = split_pos;
-                    s.len = (uint32_t)(h_pos[h] + 1 - split_pos);
-                    s.front = split_kmer;
-                    s.back.dir = h_dir[h];
-                    s.back.rc = h_rc[h];
-                    s.back.full = true;
-                    split_pos = h_pos[h] + 1 - k;
-                    split_kmer = s.back;
-                }
-                if (split_pos < ctgs[c].len) {
-                    Seg &s = *out++;
-                    s.ctg = c;
-                    s.start = split_pos;
-                    s.len = (uint32_t)(ctgs[c].len - split_pos);
-                    s.front = split_kmer;
-                    s.back = Kmer();
-                }
-            }
-        };
-        if (segs.size() >= sw.par_min)
-            pool->parallel_for(n_chunks, fill);
         else
-            for (size_t ci = 0; ci < n_chunks; ++ci)
-                fill(ci, 0);
+            for (; b < n2 && c2[b] == c; ++b) {
+                mc.push_back(c);
+                mp.push_back(p2[b]);
+                md.push_back(d2[b]);
+                mr.push_back(r2[b]);
+            }
     }
-    LAP("cut_loop");
+    h_ctg.swap(mc);
+    h_pos.swap(mp);
+    h_dir.swap(md);
+    h_rc.swap(mr);
+    n_hits = h_ctg.size();
+}
 
-    return true;
+// ---- stage 1b: cut into segments (agc_compressor.cpp:2018-2048) ----
+// The segment records are 208 bytes and a human sample has 50 k of them: they are laid out by a prefix sum over the contigs
+// and filled by the pool; only the fields the cut defines are written here -- classification (stage_classify) sets every
+// field it reads before it reads it, so records left over from the previous window need no clearing.
+void CAGCCompressor::Impl::cut_segments(BatchState &b, uint64_t n_hits)
+{
+    const std::vector<Contig> &ctgs = *b.ctgs;
+    const uint32_t n_ctg = b.n_ctg;
+    const std::vector<uint32_t> &h_ctg = scan_ctg;
+    const std::vector<uint64_t> &h_pos = scan_pos, &h_dir = scan_dir, &h_rc = scan_rc;
+    std::vector<Seg> &segs = seg_buf;
+    std::vector<uint64_t> h_begin((size_t)n_ctg + 1, 0), s_begin((size_t)n_ctg + 1, 0);
+    {
+        uint64_t h = 0;
+        for (uint32_t c = 0; c < n_ctg; ++c) {
+            h_begin[c] = h;
+            while (h < n_hits && h_ctg[h] == c)
+                ++h;
+            const uint64_t nh = h - h_begin[c];
+            const uint64_t last_split = nh ? h_pos[h - 1] + 1 - k : 0;
+            s_begin[c + 1] = s_begin[c] + nh + (last_split < ctgs[c].len ? 1 : 0);
+        }
+        h_begin[n_ctg] = h;
+    }
+    segs.resize(s_begin[n_ctg]); // (grows or shrinks by the difference to the previous window only)
+    lap(b, "cut_reserve");
+    const size_t n_chunks = std::min<size_t>(n_ctg, std::max<size_t>(1, (size_t)pool->size() * 4));
+    auto fill = [&](size_t ci, unsigned) {
+        for (uint32_t c = (uint32_t)((uint64_t)n_ctg * ci / n_chunks); c < (uint32_t)((uint64_t)n_ctg * (ci + 1) / n_chunks); ++c) {
+            uint64_t split_pos = 0;
+            Kmer split_kmer;
+            Seg *out = segs.data() + s_begin[c];
+            for (uint64_t h = h_begin[c]; h < h_begin[c + 1]; ++h) {
+                Seg &s = *out++;
+                s.ctg = c;
+                s.start = split_pos;
+                s.len = (uint32_t)(h_pos[h] + 1 - split_pos);
+                s.front = split_kmer;
+                s.back.dir = h_dir[h];
+                s.back.rc = h_rc[h];
+                s.back.full = true;
+                split_pos = h_pos[h] + 1 - k;
+                split_kmer = s.back;
+            }
+            if (split_pos < ctgs[c].len) {
+                Seg &s = *out++;
+                s.ctg = c;
+                s.start = split_pos;
+                s.len = (uint32_t)(ctgs[c].len - split_pos);
+                s.front = split_kmer;
+                s.back = Kmer();
+            }
+        }
+    };
+    if (segs.size() >= sw.par_min)
+        pool->parallel_for(n_chunks, fill);
+    else
+        for (size_t ci = 0; ci < n_chunks; ++ci)
+            fill(ci, 0);
+    lap(b, "cut_loop");
 }
 
 // add_segment for all segments at once: keys, one-splitter candidates (estimates on the GPU), missing-middle split points
 bool CAGCCompressor::Impl::stage_classify(BatchState &b)
 {
-    const std::vector<Contig> &ctgs = *b.ctgs;
-    const uint8_t *d_base = b.d_base;
-    const uint32_t n_ctg = b.n_ctg;
-    double &t0 = b.t0, &dev0 = b.dev0;
-    auto LAP = [&](const char *what) { lap(b, what); };
-    (void)ctgs; (void)d_base; (void)n_ctg; (void)t0; (void)dev0; (void)LAP;
+    lap(b, "cut");
+    Classify cl;
+    if (!classify_keys(b, cl))
+        return false;
+    stage_end(st.t_classify, st.h_classify, b.t0, b.dev0);
+    b.t0 = now();
+    lap(b, "keys");
+    if (b.overlap_encode && sw.overlap_mode == 1 && !overlap_encode_begin(b))
+        return false;
+    lap(b, "encode_begin");
+    if (!classify_estimates(b, cl))
+        return false;
+    stage_end(st.t_gpu_aux, st.h_gpu_aux, b.t0, b.dev0);
+    b.t0 = now();
+    lap(b, "estimates");
+    classify_resolve(b, cl);
+    lap(b, "resolve");
+    if (!classify_mids(b, cl))
+        return false;
+    stage_end(st.t_classify, st.h_classify, b.t0, b.dev0);
+    b.t0 = now();
+    lap(b, "mids");
+    if (!classify_split_points(b, cl))
+        return false;
+    stage_end(st.t_gpu_aux, st.h_gpu_aux, b.t0, b.dev0);
+    b.t0 = now();
+    b.dev_keys = false; // (a later pass -- revalidation -- reads the map as it is then)
+    return true;
+}
+
+// ---- stage 1c: add_segment, part 1: keys and one-splitter candidates ----
+// (the segments to classify, here and in the parts below: all of the window, or the ones whose decision read state that changed
+// since -- revalidate)
+bool CAGCCompressor::Impl::classify_keys(BatchState &b, Classify &cl)
+{
     std::vector<Seg> &segs = seg_buf;
-    LAP("cut");
-    // the segments to classify: all of the window, or the ones whose decision read state that changed since (revalidate)
     const std::vector<uint32_t> &L = b.subset;
-    // ---- stage 1c: add_segment, part 1: keys and one-splitter candidates ----
-    std::vector<Cand> cands;
+    std::vector<Cand> &cands = cl.cands;
     // (a) per segment, independent of the others: reset of the classification fields, the key of a segment with both splitters
     // and its look-up in the map -- 50 k records and as many probes of a table that does not fit the caches: the pool
     {
@@ -1739,94 +1742,94 @@ bool CAGCCompressor::Impl::stage_classify(BatchState &b)
         const bool ff = s.front.full, bf = s.back.full;
         if (ff == bf)
             continue;
-        {
-            s.back_only = !ff;
-            s.one_kmer = ff ? s.front : s.back;
-            if (s.back_only)
-                s.one_kmer.swap_dir_rc(); // :1339-1340
-            s.cand_begin = (uint32_t)cands.size();
-            auto t = terminators.find(s.one_kmer.data());
-            if (t != terminators.end()) {
-                for (uint64_t ck : t->second) {
-                    Cand c;
-                    if (ck < s.one_kmer.data()) {
-                        c.pk = {ck, s.one_kmer.data()};
-                        c.use_rc = true;
-                    } else {
-                        c.pk = {s.one_kmer.data(), ck};
-                        c.use_rc = false;
-                    }
-                    const int32_t *m = map_segments.find(c.pk);
-                    if (!m) {
-                        err("internal: terminator without group");
-                        return false;
-                    }
-                    c.gid = (uint32_t)*m;
-                    c.ref_size = groups[c.gid].ref_size;
-                    cands.push_back(c);
+        s.back_only = !ff;
+        s.one_kmer = ff ? s.front : s.back;
+        if (s.back_only)
+            s.one_kmer.swap_dir_rc(); // :1339-1340
+        s.cand_begin = (uint32_t)cands.size();
+        auto t = terminators.find(s.one_kmer.data());
+        if (t != terminators.end()) {
+            for (uint64_t ck : t->second) {
+                Cand c;
+                if (ck < s.one_kmer.data()) {
+                    c.pk = {ck, s.one_kmer.data()};
+                    c.use_rc = true;
+                } else {
+                    c.pk = {s.one_kmer.data(), ck};
+                    c.use_rc = false;
                 }
-                // stable_sort by |segment_size - ref_size|, then ref_size (:1681-1690)
-                const int64_t ssz = (int64_t)s.len;
-                std::stable_sort(cands.begin() + s.cand_begin, cands.end(), [ssz](const Cand &x, const Cand &y) {
-                    int64_t xs = (int64_t)x.ref_size, ys = (int64_t)y.ref_size;
-                    int64_t ax = std::llabs(ssz - xs), ay = std::llabs(ssz - ys);
-                    if (ax != ay)
-                        return ax < ay;
-                    return xs < ys;
-                });
+                const int32_t *m = map_segments.find(c.pk);
+                if (!m) {
+                    err("internal: terminator without group");
+                    return false;
+                }
+                c.gid = (uint32_t)*m;
+                c.ref_size = groups[c.gid].ref_size;
+                cands.push_back(c);
             }
-            s.cand_end = (uint32_t)cands.size();
-            ++st.one_splitter;
+            // stable_sort by |segment_size - ref_size|, then ref_size (:1681-1690)
+            const int64_t ssz = (int64_t)s.len;
+            std::stable_sort(cands.begin() + s.cand_begin, cands.end(), [ssz](const Cand &x, const Cand &y) {
+                int64_t xs = (int64_t)x.ref_size, ys = (int64_t)y.ref_size;
+                int64_t ax = std::llabs(ssz - xs), ay = std::llabs(ssz - ys);
+                if (ax != ay)
+                    return ax < ay;
+                return xs < ys;
+            });
         }
+        s.cand_end = (uint32_t)cands.size();
+        ++st.one_splitter;
     }
-    stage_end(st.t_classify, st.h_classify, t0, dev0);
-    t0 = now();
+    return true;
+}
 
-    LAP("keys");
-    if (b.overlap_encode && sw.overlap_mode == 1 && !overlap_encode_begin(b))
-        return false;
-    LAP("encode_begin");
-    // ---- GPU: estimates for every (one-splitter segment, candidate) pair ----
-    std::vector<uint32_t> est_cost(cands.size()), est_peak(cands.size());
-    if (!cands.empty()) {
-        // candidates without a reference in HBM (append mode: still packed) answer 0 on the host below
-        std::vector<uint32_t> gid, len, which;
-        std::vector<uint64_t> off;
-        std::vector<uint8_t> rc;
-        for (uint32_t si : L) {
-            const Seg &s = segs[si];
-            for (uint32_t c = s.cand_begin; c < s.cand_end; ++c) {
-                if (cands[c].ref_size == 0)
-                    continue;
-                which.push_back(c);
-                gid.push_back(cands[c].gid);
-                off.push_back(ctgs[s.ctg].off + s.start);
-                len.push_back(s.len);
-                // front-only: segment_dir = the segment itself; back-only: segment_dir = its reverse complement (:1317-1345)
-                rc.push_back((uint8_t)(s.back_only ? !cands[c].use_rc : cands[c].use_rc));
-                st.est_text += s.len;
-                st.est_ref += cands[c].ref_size - 1;
-            }
-        }
-        std::vector<uint32_t> cost(which.size()), peak(which.size());
-        if (!which.empty() &&
-            !hip_ok(b.pk.n_symbols ? DEVT(agc_hip_lz_estimate_batch_packed(hip, (uint32_t)which.size(), gid.data(), &b.pk, off.data(), len.data(), rc.data(),
-                                                                           cost.data(), peak.data()))
-                                   : DEVT(agc_hip_lz_estimate_batch_dev(hip, (uint32_t)which.size(), gid.data(), d_base, off.data(), len.data(), rc.data(),
-                                                                        cost.data(), peak.data())),
-                    "lz_estimate_batch"))
-            return false;
-        for (size_t i = 0; i < which.size(); ++i) {
-            est_cost[which[i]] = cost[i];
-            est_peak[which[i]] = peak[i];
-        }
-    }
-    stage_end(st.t_gpu_aux, st.h_gpu_aux, t0, dev0);
-    t0 = now();
-
-    LAP("estimates");
-    // ---- add_segment, part 2: resolve one-splitter keys (:1630-1808) ----
+// ---- GPU: estimates for every (one-splitter segment, candidate) pair ----
+bool CAGCCompressor::Impl::classify_estimates(BatchState &b, Classify &cl)
+{
+    const std::vector<Contig> &ctgs = *b.ctgs;
+    const std::vector<Seg> &segs = seg_buf;
+    const std::vector<uint32_t> &L = b.subset;
+    const std::vector<Cand> &cands = cl.cands;
+    cl.est_cost.assign(cands.size(), 0);
+    cl.est_peak.assign(cands.size(), 0);
+    if (cands.empty())
+        return true;
+    // candidates without a reference in HBM (append mode: still packed) answer 0 on the host below
+    std::vector<uint32_t> which;
+    EncodeJobs j;
     for (uint32_t si : L) {
+        const Seg &s = segs[si];
+        for (uint32_t c = s.cand_begin; c < s.cand_end; ++c) {
+            if (cands[c].ref_size == 0)
+                continue;
+            which.push_back(c);
+            // front-only: segment_dir = the segment itself; back-only: segment_dir = its reverse complement (:1317-1345)
+            j.add(cands[c].gid, ctgs[s.ctg].off + s.start, s.len, s.back_only ? !cands[c].use_rc : cands[c].use_rc);
+            st.est_text += s.len;
+            st.est_ref += cands[c].ref_size - 1;
+        }
+    }
+    std::vector<uint32_t> cost(which.size()), peak(which.size());
+    if (!which.empty() &&
+        !hip_ok(b.pk.n_symbols ? DEVT(agc_hip_lz_estimate_batch_packed(hip, j.n(), j.gid.data(), &b.pk, j.off.data(), j.len.data(), j.rc.data(),
+                                                                       cost.data(), peak.data()))
+                               : DEVT(agc_hip_lz_estimate_batch_dev(hip, j.n(), j.gid.data(), b.d_base, j.off.data(), j.len.data(), j.rc.data(),
+                                                                    cost.data(), peak.data())),
+                "lz_estimate_batch"))
+        return false;
+    for (size_t i = 0; i < which.size(); ++i) {
+        cl.est_cost[which[i]] = cost[i];
+        cl.est_peak[which[i]] = peak[i];
+    }
+    return true;
+}
+
+// ---- add_segment, part 2: resolve one-splitter keys (:1630-1808) ----
+void CAGCCompressor::Impl::classify_resolve(BatchState &b, Classify &cl)
+{
+    std::vector<Seg> &segs = seg_buf;
+    const std::vector<Cand> &cands = cl.cands;
+    for (uint32_t si : b.subset) {
         Seg &s = segs[si];
         if (s.front.full == s.back.full)
             continue;
@@ -1842,10 +1845,10 @@ bool CAGCCompressor::Impl::stage_classify(BatchState &b)
             uint64_t e;
             if (groups[cands[c].gid].ref_size == 0)
                 e = 0;
-            else if ((uint64_t)est_peak[c] > (uint32_t)best_estim)
+            else if ((uint64_t)cl.est_peak[c] > (uint32_t)best_estim)
                 e = ~0ULL; // the bounded call returned early with a value > bound: never selected
             else
-                e = est_cost[c];
+                e = cl.est_cost[c];
             v_est[i] = e;
             if (e < best_estim)
                 best_estim = e;
@@ -1870,22 +1873,21 @@ bool CAGCCompressor::Impl::stage_classify(BatchState &b)
         s.pk = best_pk;
         s.store_rc = s.back_only ? !is_best_rc : is_best_rc;
     }
+}
 
-    LAP("resolve");
-    // ---- add_segment, part 3: missing-middle-splitter candidates (:1366-1459, 1502-1627) ----
-    struct MidJob {
-        uint32_t seg, gid1, gid2;
-        uint8_t rc1, pf1, rc2, pf2;
-    };
-    std::vector<MidJob> mids;
-    {
-        // the segments are independent here (the map and the terminator lists are only read): chunks of the list go to the pool,
-        // the jobs they produce are numbered afterwards in segment order
-        const size_t nL = L.size(), n_chunks = nL >= sw.par_min ? std::min<size_t>(std::max<size_t>(nL / 1024, 2), (size_t)pool->size() * 4) : 1;
-        std::vector<std::vector<MidJob>> chunk_jobs(n_chunks);
-        std::vector<uint64_t> chunk_tried(n_chunks, 0);
-        std::vector<uint8_t> chunk_bad(n_chunks, 0);
-        auto one = [&](uint32_t si, std::vector<MidJob> &out, uint64_t &tried, bool &bad) {
+// ---- add_segment, part 3: missing-middle-splitter candidates (:1366-1459, 1502-1627) ----
+// the segments are independent here (the map and the terminator lists are only read): chunks of the list go to the pool,
+// the jobs they produce are numbered afterwards in segment order
+bool CAGCCompressor::Impl::classify_mids(BatchState &b, Classify &cl)
+{
+    std::vector<Seg> &segs = seg_buf;
+    const std::vector<uint32_t> &L = b.subset;
+    std::vector<MidJob> &mids = cl.mids;
+    const size_t nL = L.size(), n_chunks = nL >= sw.par_min ? std::min<size_t>(std::max<size_t>(nL / 1024, 2), (size_t)pool->size() * 4) : 1;
+    std::vector<std::vector<MidJob>> chunk_jobs(n_chunks);
+    std::vector<uint64_t> chunk_tried(n_chunks, 0);
+    std::vector<uint8_t> chunk_bad(n_chunks, 0);
+    auto one = [&](uint32_t si, std::vector<MidJob> &out, uint64_t &tried, bool &bad) {
         Seg &s = segs[si];
         if (concatenated || s.pk.first == NO_KMER || s.pk.second == NO_KMER)
             return;
@@ -1957,32 +1959,37 @@ bool CAGCCompressor::Impl::stage_classify(BatchState &b)
         j.rc2 = (uint8_t)(m_lt_b ? s.use_rc : !s.use_rc);
         j.pf2 = m_lt_b ? 0 : 1;
         out.push_back(j); // (its index in the job list is given out below, in segment order)
-            };
-        auto run_chunk = [&](size_t ci, unsigned) {
-            bool bad = false;
-            for (size_t t = nL * ci / n_chunks; t < nL * (ci + 1) / n_chunks && !bad; ++t)
-                one(L[t], chunk_jobs[ci], chunk_tried[ci], bad);
-            chunk_bad[ci] = bad;
-        };
-        if (n_chunks > 1)
-            pool->parallel_for(n_chunks, run_chunk);
-        else
-            run_chunk(0, 0);
-        for (size_t ci = 0; ci < n_chunks; ++ci) {
-            if (chunk_bad[ci]) {
-                err("internal: shared terminator without group");
-                return false;
-            }
-            st.middle_tried += chunk_tried[ci];
-            for (const MidJob &j : chunk_jobs[ci]) {
-                segs[j.seg].mid_job = (int32_t)mids.size();
-                mids.push_back(j);
-            }
+    };
+    auto run_chunk = [&](size_t ci, unsigned) {
+        bool bad = false;
+        for (size_t t = nL * ci / n_chunks; t < nL * (ci + 1) / n_chunks && !bad; ++t)
+            one(L[t], chunk_jobs[ci], chunk_tried[ci], bad);
+        chunk_bad[ci] = bad;
+    };
+    if (n_chunks > 1)
+        pool->parallel_for(n_chunks, run_chunk);
+    else
+        run_chunk(0, 0);
+    for (size_t ci = 0; ci < n_chunks; ++ci) {
+        if (chunk_bad[ci]) {
+            err("internal: shared terminator without group");
+            return false;
+        }
+        st.middle_tried += chunk_tried[ci];
+        for (const MidJob &j : chunk_jobs[ci]) {
+            segs[j.seg].mid_job = (int32_t)mids.size();
+            mids.push_back(j);
         }
     }
-    stage_end(st.t_classify, st.h_classify, t0, dev0);
-    t0 = now();
-    LAP("mids");
+    return true;
+}
+
+// the split points of the missing-middle candidates (GPU)
+bool CAGCCompressor::Impl::classify_split_points(BatchState &b, Classify &cl)
+{
+    const std::vector<Contig> &ctgs = *b.ctgs;
+    std::vector<Seg> &segs = seg_buf;
+    const std::vector<MidJob> &mids = cl.mids;
     std::vector<uint32_t> best_pos(mids.size(), 0);
     // While this thread waits for the split points (4-5 ms at human scale) a helper places every segment that has no split-point
     // job -- what stage_place would do for it, minus the part number: the host phase between the classification kernels and the
@@ -2044,7 +2051,7 @@ bool CAGCCompressor::Impl::stage_classify(BatchState &b)
         }
         if (!hip_ok(b.pk.n_symbols ? DEVT(agc_hip_lz_split_point_batch_packed(hip, (uint32_t)n, g1.data(), g2.data(), &b.pk, off.data(), len.data(), r1.data(),
                                                                               p1.data(), r2.data(), p2.data(), best_pos.data(), nullptr))
-                                   : DEVT(agc_hip_lz_split_point_batch_dev(hip, (uint32_t)n, g1.data(), g2.data(), d_base, off.data(), len.data(), r1.data(),
+                                   : DEVT(agc_hip_lz_split_point_batch_dev(hip, (uint32_t)n, g1.data(), g2.data(), b.d_base, off.data(), len.data(), r1.data(),
                                                                            p1.data(), r2.data(), p2.data(), best_pos.data(), nullptr)),
                     "lz_split_point_batch"))
             return false;
@@ -2055,10 +2062,6 @@ bool CAGCCompressor::Impl::stage_classify(BatchState &b)
     }
     for (size_t i = 0; i < mids.size(); ++i)
         segs[mids[i].seg].bp = best_pos[i];
-    stage_end(st.t_gpu_aux, st.h_gpu_aux, t0, dev0);
-    t0 = now();
-    b.dev_keys = false; // (a later pass -- revalidation -- reads the map as it is then)
-
     return true;
 }
 
@@ -2076,13 +2079,8 @@ void CAGCCompressor::Impl::finish_spec_fill(BatchState &b)
 bool CAGCCompressor::Impl::stage_place(BatchState &b)
 {
     const std::vector<Contig> &ctgs = *b.ctgs;
-    const uint8_t *d_base = b.d_base;
-    const uint32_t n_ctg = b.n_ctg;
-    double &t0 = b.t0, &dev0 = b.dev0;
-    auto LAP = [&](const char *what) { lap(b, what); };
-    (void)ctgs; (void)d_base; (void)n_ctg; (void)t0; (void)dev0; (void)LAP;
     std::vector<Seg> &segs = seg_buf;
-    LAP("splitpoints");
+    lap(b, "splitpoints");
     finish_spec_fill(b);
     // the announced next sample: its expansion + scan are queued NOW -- the classification kernels of this sample are done, what
     // follows is host work (placement, ordering, new group ids: ~2.5 ms at human scale) before the encode needs the GPU again
@@ -2198,13 +2196,10 @@ bool CAGCCompressor::Impl::stage_place(BatchState &b)
 bool CAGCCompressor::Impl::stage_register(BatchState &b)
 {
     const std::vector<Contig> &ctgs = *b.ctgs;
-    const uint8_t *d_base = b.d_base;
     const uint32_t n_ctg = b.n_ctg;
     double &t0 = b.t0, &dev0 = b.dev0;
-    auto LAP = [&](const char *what) { lap(b, what); };
-    (void)ctgs; (void)d_base; (void)n_ctg; (void)t0; (void)dev0; (void)LAP;
     std::vector<Placed> &placed = placed_buf;
-    LAP("placement");
+    lap(b, "placement");
     // ---- speculation window: the contigs may belong to several consecutive samples that were
     // all classified against the SAME state.  State changes only when a sample mints a new group (or, in append mode,
     // unpacks one), so the classification is valid for every sample up to and including the first one that does; this
@@ -2241,7 +2236,7 @@ bool CAGCCompressor::Impl::stage_register(BatchState &b)
             ctg_rank[co[i]] = r;
         }
     }
-    LAP("ctg_rank");
+    lap(b, "ctg_rank");
     std::vector<uint32_t> &order = b.order; // committed items only, in (sample, contig name, part) order
     {
         std::vector<std::pair<uint64_t, uint32_t>> keyed;
@@ -2284,8 +2279,8 @@ bool CAGCCompressor::Impl::stage_register(BatchState &b)
         }
         st.segments += order.size();
     }
+    lap(b, "order");
     {
-    LAP("order");
         // new group ids in that order (only the last committed sample can have new items)
         std::map<pk_t, uint32_t> m_kmers;
         uint32_t gid = no_segments;
@@ -2306,7 +2301,7 @@ bool CAGCCompressor::Impl::stage_register(BatchState &b)
         no_segments += no_new;
         st.new_groups += no_new;
     }
-    LAP("newgids");
+    lap(b, "newgids");
     // per sample: lists of items per group, raw groups by distribute_segments(0, 0, 16) on the sorted
     // list of group 0 (agc_compressor.h:417-435)
     std::vector<SampleLists> &per_sample = b.per_sample;
@@ -2361,6 +2356,28 @@ bool CAGCCompressor::Impl::stage_register(BatchState &b)
     return true;
 }
 
+// the repetitiveness probe of nr new references from their lag counters (28 each), with the reference's double arithmetic
+// (segment.h:224-247)
+static void repetitive_from_lags(const uint32_t *lag_cnt, const uint32_t *lag_cur, size_t nr, std::vector<uint8_t> &repetitive)
+{
+    repetitive.assign(nr, 0);
+    for (size_t fi = 0; fi < nr; ++fi) {
+        double best_frac = 0.0;
+        for (uint32_t l = 0; l < 28; ++l) {
+            const uint32_t cnt = lag_cnt[fi * 28 + l], cur = lag_cur[fi * 28 + l];
+            double frac = 0.0;
+            if (cur)
+                frac = (double)cnt / cur;
+            if (frac > best_frac) {
+                best_frac = frac;
+                if (best_frac >= 0.5)
+                    break;
+            }
+        }
+        repetitive[fi] = !(best_frac < 0.5);
+    }
+}
+
 // store_segments, first half: new references into HBM, LZ-encode of everything else, then the bookkeeping stage
 bool CAGCCompressor::Impl::stage_store(BatchState &b) { return stage_store_head(b) && stage_store_finish(b); }
 
@@ -2370,12 +2387,9 @@ bool CAGCCompressor::Impl::stage_store(BatchState &b) { return stage_store_head(
 bool CAGCCompressor::Impl::stage_store_head(BatchState &b)
 {
     const uint8_t *d_base = b.d_base;
-    double &t0 = b.t0, &dev0 = b.dev0;
-    auto LAP = [&](const char *what) { lap(b, what); };
-    (void)t0; (void)dev0;
     std::vector<Placed> &placed = placed_buf;
     std::vector<SampleLists> &per_sample = b.per_sample;
-    LAP("per_sample");
+    lap(b, "per_sample");
     // (a) what each item needs: new groups' first item becomes the reference (segment.cpp:39-48), raw
     // groups keep the symbols, everything else is LZ-encoded -- decided per group across the committed samples
     std::vector<uint32_t> &new_ref_items = b.sto.new_ref_items; // placed indices, one per new group with items
@@ -2401,7 +2415,7 @@ bool CAGCCompressor::Impl::stage_store_head(BatchState &b)
                 }
             }
     }
-    LAP("classes");
+    lap(b, "classes");
     // append mode: the first add to a group of the input archive unpacks it (segment.cpp:19-20, 39-40)
     if (appending)
         for (uint32_t sidx = 0; sidx < per_sample.size(); ++sidx)
@@ -2420,7 +2434,7 @@ bool CAGCCompressor::Impl::stage_store_head(BatchState &b)
             b.changed.push_back(placed[idx].pk.second);
         }
     }
-    LAP("note_new_groups");
+    lap(b, "note_new_groups");
     // GPU: what the host must pack of the new references and raw items, and the repetitiveness probe of the references
     std::vector<uint32_t> lag_cnt, lag_cur;
     std::vector<uint8_t> &repetitive = b.sto.repetitive;
@@ -2434,23 +2448,21 @@ bool CAGCCompressor::Impl::stage_store_head(BatchState &b)
     // them (finish_ref_store) -- a one-block kernel queued behind the announced scan and the FASTA conversion took 1.4 ms to come
     // back, three round trips a step.  The reference sample's GBs of new references take the calls below as before.
     bool ref_async = false;
+    auto slices = [&](size_t n) { // the first n of: the new references, then the raw items
+        EncodeJobs j;
+        for (size_t i = 0; i < n; ++i) {
+            const Placed &pl = placed[i < new_ref_items.size() ? new_ref_items[i] : raw_items[i - new_ref_items.size()]];
+            j.add(0, pl.off, pl.len, pl.rc);
+        }
+        return j;
+    };
     if (sw.ref_store_async && dist_world == 1 && book_can_async(b.n_samples) && b.pk.n_symbols && new_ref_items.size() + raw_items.size() > 0) {
         const size_t nr = new_ref_items.size(), nf = nr + raw_items.size();
-        uint64_t tot = 0;
-        for (size_t i = 0; i < nf; ++i)
-            tot += placed[i < nr ? new_ref_items[i] : raw_items[i - nr]].len;
+        const EncodeJobs j = slices(nf);
+        const uint64_t tot = j.tot;
         if (tot <= (64ull << 20)) {
-            std::vector<uint32_t> len(nf);
-            std::vector<uint64_t> off(nf);
-            std::vector<uint8_t> rc(nf);
-            for (size_t i = 0; i < nf; ++i) {
-                const Placed &pl = placed[i < nr ? new_ref_items[i] : raw_items[i - nr]];
-                off[i] = pl.off;
-                len[i] = pl.len;
-                rc[i] = pl.rc;
-                if (i < nr)
-                    st.ref_bytes += pl.len;
-            }
+            for (size_t i = 0; i < nr; ++i)
+                st.ref_bytes += j.len[i];
             const uint32_t slot = ref_pin_next;
             PinnedBytes &pin = ref_pin[slot];
             if (!pin.ctx)
@@ -2461,7 +2473,7 @@ bool CAGCCompressor::Impl::stage_store_head(BatchState &b)
                 return false;
             }
             fetched_off.resize(nf + 1);
-            if (!hip_ok(DEVT(agc_hip_ref_store_begin_packed(hip, slot, (uint32_t)nr, (uint32_t)nf, &b.pk, off.data(), len.data(), rc.data(), (uint32_t *)pin.data(),
+            if (!hip_ok(DEVT(agc_hip_ref_store_begin_packed(hip, slot, (uint32_t)nr, (uint32_t)nf, &b.pk, j.off.data(), j.len.data(), j.rc.data(), (uint32_t *)pin.data(),
                                                             (uint32_t *)(pin.data() + cnt_bytes), pin.data() + 2 * cnt_bytes, tot, fetched_off.data())),
                         "ref_store_begin"))
                 return false;
@@ -2470,74 +2482,41 @@ bool CAGCCompressor::Impl::stage_store_head(BatchState &b)
             b.sto.ref_nr = nr;
             b.sto.ref_pin = &pin;
             ref_async = true;
-            LAP("lag_counts + fetch_slices (queued)");
+            lap(b, "lag_counts + fetch_slices (queued)");
         }
     }
     if (!ref_async) {
         const size_t nr = new_ref_items.size();
         if (nr) {
-            std::vector<uint32_t> len(nr);
-            std::vector<uint64_t> off(nr);
-            std::vector<uint8_t> rc(nr);
-            for (size_t i = 0; i < nr; ++i) {
-                const Placed &pl = placed[new_ref_items[i]];
-                off[i] = pl.off;
-                len[i] = pl.len;
-                rc[i] = pl.rc;
-                st.ref_bytes += pl.len;
-            }
+            const EncodeJobs j = slices(nr);
+            st.ref_bytes += j.tot;
             lag_cnt.resize(nr * 28);
             lag_cur.resize(nr * 28);
-            if (!hip_ok(b.pk.n_symbols ? DEVT(agc_hip_ref_lag_counts_packed(hip, (uint32_t)nr, &b.pk, off.data(), len.data(), rc.data(), lag_cnt.data(), lag_cur.data()))
-                                       : DEVT(agc_hip_ref_lag_counts_dev(hip, (uint32_t)nr, d_base, off.data(), len.data(), rc.data(), lag_cnt.data(), lag_cur.data())),
+            if (!hip_ok(b.pk.n_symbols ? DEVT(agc_hip_ref_lag_counts_packed(hip, (uint32_t)nr, &b.pk, j.off.data(), j.len.data(), j.rc.data(), lag_cnt.data(), lag_cur.data()))
+                                       : DEVT(agc_hip_ref_lag_counts_dev(hip, (uint32_t)nr, d_base, j.off.data(), j.len.data(), j.rc.data(), lag_cnt.data(), lag_cur.data())),
                         "ref_lag_counts"))
                 return false;
-            // repetitiveness probe with the reference's double arithmetic (segment.h:224-247)
-            repetitive.resize(nr);
-            for (size_t fi = 0; fi < nr; ++fi) {
-                double best_frac = 0.0;
-                for (uint32_t l = 0; l < 28; ++l) {
-                    const uint32_t cnt = lag_cnt[fi * 28 + l], cur = lag_cur[fi * 28 + l];
-                    double frac = 0.0;
-                    if (cur)
-                        frac = (double)cnt / cur;
-                    if (frac > best_frac) {
-                        best_frac = frac;
-                        if (best_frac >= 0.5)
-                            break;
-                    }
-                }
-                repetitive[fi] = !(best_frac < 0.5);
-            }
-            LAP("lag_counts");
+            repetitive_from_lags(lag_cnt.data(), lag_cur.data(), nr, repetitive);
+            lap(b, "lag_counts");
         }
         const size_t nf = nr + raw_items.size();
         if (nf) {
-            std::vector<uint32_t> len(nf);
-            std::vector<uint64_t> off(nf);
-            std::vector<uint8_t> rc(nf);
-            uint64_t tot = 0;
-            for (size_t i = 0; i < nf; ++i) {
-                const Placed &pl = placed[i < nr ? new_ref_items[i] : raw_items[i - nr]];
-                off[i] = pl.off;
-                len[i] = pl.len;
-                rc[i] = pl.rc;
-                tot += pl.len;
-            }
+            const EncodeJobs j = slices(nf);
+            const uint64_t tot = j.tot;
             if (fetched.size() < tot)
                 fetched.resize(tot);
             fetched_off.resize(nf + 1);
-            if (!hip_ok(b.pk.n_symbols ? DEVT(agc_hip_fetch_slices_packed(hip, (uint32_t)nf, &b.pk, off.data(), len.data(), rc.data(), fetched.data(), tot, fetched_off.data()))
-                                       : DEVT(agc_hip_fetch_slices_dev(hip, (uint32_t)nf, d_base, off.data(), len.data(), rc.data(), fetched.data(), tot, fetched_off.data())),
+            if (!hip_ok(b.pk.n_symbols ? DEVT(agc_hip_fetch_slices_packed(hip, (uint32_t)nf, &b.pk, j.off.data(), j.len.data(), j.rc.data(), fetched.data(), tot, fetched_off.data()))
+                                       : DEVT(agc_hip_fetch_slices_dev(hip, (uint32_t)nf, d_base, j.off.data(), j.len.data(), j.rc.data(), fetched.data(), tot, fetched_off.data())),
                         "fetch_slices"))
                 return false;
         }
     }
-    LAP("fetch_slices");
+    lap(b, "fetch_slices");
     if (dist_world > 1) {
         if (!make_record_head(b))
             return false;
-        LAP("record head");
+        lap(b, "record head");
     }
     return true;
 }
@@ -2545,259 +2524,226 @@ bool CAGCCompressor::Impl::stage_store_head(BatchState &b)
 // second half: the new references' index on this GPU, the deltas, the bookkeeping (and the body of the commit record)
 bool CAGCCompressor::Impl::stage_store_finish(BatchState &b)
 {
-    const uint8_t *d_base = b.d_base;
-    double &t0 = b.t0, &dev0 = b.dev0;
-    auto LAP = [&](const char *what) { lap(b, what); };
-    std::vector<Placed> &placed = placed_buf;
-    const uint32_t commit_upto = b.commit_upto;
-    std::vector<SampleLists> &per_sample = b.per_sample;
-    std::vector<uint32_t> &new_ref_items = b.sto.new_ref_items, &raw_items = b.sto.raw_items, &enc_items = b.sto.enc_items;
-    bytes_t &fetched = fetch_buf;
     // the previous registration's task is done with the second buffer set and with the device's second lane (long ago: it was
     // queued a whole step earlier)
     if (!book_wait_seq(last_own_seq))
         return false;
     // ... and the early collection of this sample's whole-sample encode (done since the kernel ended, a few ms ago)
-    const bool early_done = b.early_seq != 0 && b.dev_enc_n != 0;
+    StoreFinish f;
+    f.early_done = b.early_seq != 0 && b.dev_enc_n != 0;
     if (b.early_seq != 0 && (!book_wait_seq(b.early_seq) || !early_enc.ok))
         return false;
-    const bool hand_over = book_can_async(b.n_samples) && (dist_world == 1 || dist_rank == dist_writer);
-    {
-        const size_t nr = new_ref_items.size();
-        if (nr) { // register the new references (index build)
-            std::vector<uint32_t> gid(nr), len(nr);
-            std::vector<uint64_t> off(nr);
-            std::vector<uint8_t> rc(nr);
-            for (size_t i = 0; i < nr; ++i) {
-                const Placed &pl = placed[new_ref_items[i]];
-                gid[i] = (uint32_t)pl.gid;
-                off[i] = pl.off;
-                len[i] = pl.len;
-                rc[i] = pl.rc;
-            }
-            if (!hip_ok(b.pk.n_symbols ? DEVT(agc_hip_ref_register_batch_packed(hip, (uint32_t)nr, gid.data(), &b.pk, off.data(), len.data(), rc.data(), mml))
-                                       : DEVT(agc_hip_ref_register_batch_dev(hip, (uint32_t)nr, gid.data(), d_base, off.data(), len.data(), rc.data(), mml)),
-                        "ref_register_batch"))
-                return false;
-            LAP("ref_register");
-        }
-    }
-    stage_end(st.t_register, st.h_register, t0, dev0);
-    t0 = now();
+    f.hand_over = book_can_async(b.n_samples) && (dist_world == 1 || dist_rank == dist_writer);
+    if (!register_new_refs(b))
+        return false;
+    stage_end(st.t_register, st.h_register, b.t0, b.dev0);
+    b.t0 = now();
     // LZ deltas (segment.cpp:50-58): items whose group already had its reference when the window was classified were encoded
     // up front in one batch (spec_encode); only the others -- followers of a group minted in this window, segments that a
     // revalidation placed differently -- are encoded now
-    std::vector<const uint8_t *> enc_ptr(enc_items.size(), nullptr);
-    std::vector<uint32_t> enc_len(enc_items.size(), 0);
+    f.enc_ptr.assign(b.sto.enc_items.size(), nullptr);
+    f.enc_len.assign(b.sto.enc_items.size(), 0);
     if (b.enc_in_flight && !overlap_encode_end(b))
         return false;
-    LAP("encode_end");
-    std::vector<uint32_t> enc_later; // per result of the encode in flight on the second lane: its position in enc_items (~0u: unused)
-    uint64_t enc_later_text = 0;
-    std::vector<uint32_t> enc_later2; // ... and of the one launched below on lane 1 while lane 0 still holds the whole-sample encode
-    uint64_t enc_later2_text = 0;
+    lap(b, "encode_end");
     // the device launched the encode of the segments whose group it knew (stage_scan_dev).  Its deltas are first read by the
     // bookkeeping task, which then collects them beside the next sample -- unless there is no such task (several registrations in
     // the window do not reach here with one in flight; -c, append, AGC_AMD_ASYNC_BOOK=0) or this is the N-rank mode, where the
     // record's body is made below and holds every delta: then they are collected now, behind the window's other speculative
     // deltas, and are ordinary speculative deltas from here on
-    if (b.dev_enc_n != 0 && (!hand_over || dist_world > 1)) {
-        const size_t ne = b.dev_enc_n;
-        std::vector<uint64_t> eoff(ne + 1, 0);
-        const uint64_t base = b.spec_bytes;
-        uint64_t cap = std::max<uint64_t>(enc_buf.size() > base ? enc_buf.size() - base : 0, (uint64_t)1 << 16);
-        if (early_done) { // (collected already, at the start of enc_buf: an early task is only queued with spec_bytes == 0)
-            if (base != 0 || early_enc.eoff.size() != ne + 1) {
-                err("internal: early collection of the encode does not match the registration");
-                return false;
-            }
-            eoff = early_enc.eoff;
-        }
-        for (; !early_done;) {
-            if (!enc_buf.resize(base + cap)) {
-                err("out of memory (delta buffer)");
-                return false;
-            }
-            const int r = DEVT(agc_hip_lz_encode_end(hip, enc_buf.data() + base, cap, eoff.data()));
-            if (r == AGC_HIP_ECAP) {
-                cap = eoff[ne] + eoff[ne] / 8 + 4096;
-                continue;
-            }
-            lane2_release();
-            if (!hip_ok(r, "lz_encode_end"))
-                return false;
-            break;
-        }
-        for (BatchState::Spec &sp : b.spec)
-            if (sp.valid && sp.pending >= 0) {
-                sp.enc_off = base + eoff[(size_t)sp.pending];
-                sp.enc_len = (uint32_t)(eoff[(size_t)sp.pending + 1] - eoff[(size_t)sp.pending]);
-                sp.pending = -1;
-            }
-        b.spec_bytes = base + eoff[ne];
-        if (!early_done) // (an early task's bytes are counted by the book thread)
-            st.delta_bytes += eoff[ne];
-        b.dev_enc_n = 0;
-        LAP("encode of the known segments collected");
-    }
-    const bool bulk = b.dev_enc_n != 0;
-    if (bulk)
-        enc_later.assign(b.dev_enc_n, ~0u);
-    {
-        std::vector<uint32_t> todo; // positions in enc_items
-        for (uint32_t i = 0; i < enc_items.size(); ++i) {
-            const Placed &pl = placed[enc_items[i]];
-            const BatchState::Spec *sp = pl.key < b.spec.size() ? &b.spec[pl.key] : nullptr;
-            if (sp && sp->valid && sp->gid == (uint32_t)pl.gid && sp->off == pl.off && sp->len == pl.len && sp->rc == pl.rc) {
-                if (sp->pending >= 0) {
-                    enc_later[(uint32_t)sp->pending] = i;
-                    enc_later_text += pl.len;
-                } else {
-                    enc_ptr[i] = enc_buf.data() + sp->enc_off;
-                    enc_len[i] = sp->enc_len;
-                }
-            } else
-                todo.push_back(i);
-        }
-        if (!todo.empty()) {
-            const size_t ne = todo.size();
-            std::vector<uint32_t> gid(ne), len(ne);
-            std::vector<uint64_t> off(ne), eoff(ne + 1, 0);
-            std::vector<uint8_t> rc(ne);
-            uint64_t tot = 0;
-            for (size_t i = 0; i < ne; ++i) {
-                const Placed &pl = placed[enc_items[todo[i]]];
-                gid[i] = (uint32_t)pl.gid;
-                off[i] = pl.off;
-                len[i] = pl.len;
-                rc[i] = pl.rc;
-                tot += pl.len;
-                st.enc_text += pl.len;
-                st.enc_ref += groups[pl.gid].ref_size ? groups[pl.gid].ref_size - 1 : 0;
-            }
-            // The encode is only LAUNCHED here when its result is first read by the bookkeeping task: the task collects it (second
-            // device lane) while this thread goes on with the next sample.  Needs a sample in a staging buffer the device context
-            // owns (it outlives the call) and nothing else on that lane.
-            const bool later = hand_over && sw.async_encode && dist_world == 1 && b.base_owned && b.pk.n_symbols && sw.overlap_mode == 0 && !b.enc_in_flight && b.spec_bytes == 0;
-            if (!bulk && later) {
-                lane2_acquire();
-                if (!hip_ok(DEVT(agc_hip_lz_encode_begin_packed(hip, (uint32_t)ne, gid.data(), &b.pk, off.data(), len.data(), rc.data())), "lz_encode_begin")) {
-                    lane2_release();
-                    return false;
-                }
-                enc_later.swap(todo);
-                enc_later_text = tot;
-                st.lz_encoded += ne;
-            } else if (bulk && later) {
-                // (lane 0 carries the encode of the segments the device knew; these -- followers of the groups this sample minted,
-                // whose references were indexed a moment ago -- go to lane 1 and are collected by the same task)
-                lane2_acquire(1);
-                if (!hip_ok(DEVT(agc_hip_lz_encode_begin_packed_on(hip, 1, (uint32_t)ne, gid.data(), &b.pk, off.data(), len.data(), rc.data())), "lz_encode_begin")) {
-                    lane2_release(1);
-                    return false;
-                }
-                enc_later2.swap(todo);
-                enc_later2_text = tot;
-                st.lz_encoded += ne;
-            } else {
-            PinnedBytes &enc = enc_buf2;
-            uint64_t cap = std::max<uint64_t>(enc.size(), tot / 64 + (1u << 16));
-            for (;;) {
-                if (enc.size() < cap)
-                    enc.resize(cap);
-                int r = b.pk.n_symbols ? DEVT(agc_hip_lz_encode_batch_packed(hip, (uint32_t)ne, gid.data(), &b.pk, off.data(), len.data(), rc.data(), enc.data(), cap,
-                                                                              eoff.data()))
-                                       : DEVT(agc_hip_lz_encode_batch_dev(hip, (uint32_t)ne, gid.data(), d_base, off.data(), len.data(), rc.data(), enc.data(), cap,
-                                                                          eoff.data()));
-                if (r == AGC_HIP_ECAP) {
-                    cap = eoff[ne] + eoff[ne] / 8 + 4096; // (headroom: the next sample's deltas are a little longer, and a retry runs the kernel again)
-                    continue;
-                }
-                if (!hip_ok(r, "lz_encode_batch"))
-                    return false;
-                break;
-            }
-            for (size_t i = 0; i < ne; ++i) {
-                enc_ptr[todo[i]] = enc.data() + eoff[i];
-                enc_len[todo[i]] = (uint32_t)(eoff[i + 1] - eoff[i]);
-            }
-            st.lz_encoded += ne;
-            st.delta_bytes += eoff[ne];
-            }
-        }
-    }
-    LAP(enc_later.empty() && enc_later2.empty() ? "encode" : "encode (in flight)");
-    stage_end(st.t_encode, st.h_encode, t0, dev0);
-    t0 = now();
-
+    if (b.dev_enc_n != 0 && (!f.hand_over || dist_world > 1) && !collect_known_encode(b, f.early_done))
+        return false;
+    f.bulk = b.dev_enc_n != 0;
+    if (!encode_rest(b, f))
+        return false;
+    lap(b, f.enc_later.empty() && f.enc_later2.empty() ? "encode" : "encode (in flight)");
+    stage_end(st.t_encode, st.h_encode, b.t0, b.dev0);
+    b.t0 = now();
     CommitData cdta;
+    build_commit(b, f, cdta);
+    if (dist_world > 1) {
+        if (!make_record_body(cdta))
+            return false;
+        lap(b, "record body");
+        if (dist_rank != dist_writer)
+            return true; // the writer rank does the bookkeeping from the record
+    }
+    if (f.hand_over)
+        return hand_over_books(b, f, cdta);
+    const bool ok = book_wait() && finish_ref_store(cdta, fetch_buf) && book_and_store(cdta);
+    lap(b, "book_and_store");
+    return ok;
+}
+
+// the new references of the commit run get their index on the device
+bool CAGCCompressor::Impl::register_new_refs(BatchState &b)
+{
+    const EncodeJobs j = encode_jobs(b.sto.new_ref_items, false);
+    if (!j.n())
+        return true;
+    if (!hip_ok(b.pk.n_symbols ? DEVT(agc_hip_ref_register_batch_packed(hip, j.n(), j.gid.data(), &b.pk, j.off.data(), j.len.data(), j.rc.data(), mml))
+                               : DEVT(agc_hip_ref_register_batch_dev(hip, j.n(), j.gid.data(), b.d_base, j.off.data(), j.len.data(), j.rc.data(), mml)),
+                "ref_register_batch"))
+        return false;
+    lap(b, "ref_register");
+    return true;
+}
+
+// the device-launched encode is collected by the registration itself (or was, by the early task): its deltas go behind the
+// window's other speculative deltas and are ordinary speculative deltas from here on
+bool CAGCCompressor::Impl::collect_known_encode(BatchState &b, bool early_done)
+{
+    const size_t ne = b.dev_enc_n;
+    std::vector<uint64_t> eoff;
+    const uint64_t base = b.spec_bytes;
+    if (early_done) { // (collected already, at the start of enc_buf: an early task is only queued with spec_bytes == 0)
+        if (base != 0 || early_enc.eoff.size() != ne + 1) {
+            err("internal: early collection of the encode does not match the registration");
+            return false;
+        }
+        eoff = early_enc.eoff;
+    } else {
+        const bool ok = collect_lane(-1, enc_buf, base, std::max<uint64_t>(enc_buf.size() > base ? enc_buf.size() - base : 0, (uint64_t)1 << 16), ne, eoff);
+        lane2_release();
+        if (!ok)
+            return false;
+    }
+    for (BatchState::Spec &sp : b.spec)
+        if (sp.valid && sp.pending >= 0) {
+            sp.enc_off = base + eoff[(size_t)sp.pending];
+            sp.enc_len = (uint32_t)(eoff[(size_t)sp.pending + 1] - eoff[(size_t)sp.pending]);
+            sp.pending = -1;
+        }
+    b.spec_bytes = base + eoff[ne];
+    if (!early_done) // (an early task's bytes are counted by the book thread)
+        st.delta_bytes += eoff[ne];
+    b.dev_enc_n = 0;
+    lap(b, "encode of the known segments collected");
+    return true;
+}
+
+// the placed items that are LZ-encoded are matched to the speculative deltas; the rest is encoded (or its encode launched) now
+bool CAGCCompressor::Impl::encode_rest(BatchState &b, StoreFinish &f)
+{
+    const std::vector<Placed> &placed = placed_buf;
+    const std::vector<uint32_t> &enc_items = b.sto.enc_items;
+    if (f.bulk)
+        f.enc_later.assign(b.dev_enc_n, ~0u);
+    std::vector<uint32_t> todo, todo_items; // positions in enc_items, and the placed items there
+    for (uint32_t i = 0; i < enc_items.size(); ++i) {
+        const Placed &pl = placed[enc_items[i]];
+        const BatchState::Spec *sp = pl.key < b.spec.size() ? &b.spec[pl.key] : nullptr;
+        if (sp && sp->valid && sp->gid == (uint32_t)pl.gid && sp->off == pl.off && sp->len == pl.len && sp->rc == pl.rc) {
+            if (sp->pending >= 0) {
+                f.enc_later[(uint32_t)sp->pending] = i;
+                f.enc_later_text += pl.len;
+            } else {
+                f.enc_ptr[i] = enc_buf.data() + sp->enc_off;
+                f.enc_len[i] = sp->enc_len;
+            }
+        } else {
+            todo.push_back(i);
+            todo_items.push_back(enc_items[i]);
+        }
+    }
+    if (todo.empty())
+        return true;
+    const EncodeJobs j = encode_jobs(todo_items);
+    const size_t ne = todo.size();
+    // The encode is only LAUNCHED here when its result is first read by the bookkeeping task: the task collects it (second
+    // device lane) while this thread goes on with the next sample.  Needs a sample in a staging buffer the device context
+    // owns (it outlives the call) and nothing else on that lane.
+    const bool later = f.hand_over && sw.async_encode && dist_world == 1 && b.base_owned && b.pk.n_symbols && sw.overlap_mode == 0 && !b.enc_in_flight && b.spec_bytes == 0;
+    if (later) {
+        // (bulk: lane 0 carries the encode of the segments the device knew; these -- followers of the groups this sample minted,
+        // whose references were indexed a moment ago -- go to lane 1 and are collected by the same task)
+        const int lane = f.bulk ? 1 : 0;
+        lane2_acquire(lane);
+        if (!hip_ok(f.bulk ? DEVT(agc_hip_lz_encode_begin_packed_on(hip, 1, j.n(), j.gid.data(), &b.pk, j.off.data(), j.len.data(), j.rc.data()))
+                           : DEVT(agc_hip_lz_encode_begin_packed(hip, j.n(), j.gid.data(), &b.pk, j.off.data(), j.len.data(), j.rc.data())),
+                    "lz_encode_begin")) {
+            lane2_release(lane);
+            return false;
+        }
+        (f.bulk ? f.enc_later2 : f.enc_later).swap(todo);
+        (f.bulk ? f.enc_later2_text : f.enc_later_text) = j.tot;
+        st.lz_encoded += ne;
+        return true;
+    }
+    std::vector<uint64_t> eoff;
+    if (!encode_now(b, j, enc_buf2, 0, std::max<uint64_t>(enc_buf2.size(), j.tot / 64 + (1u << 16)), eoff))
+        return false;
+    for (size_t i = 0; i < ne; ++i) {
+        f.enc_ptr[todo[i]] = enc_buf2.data() + eoff[i];
+        f.enc_len[todo[i]] = (uint32_t)(eoff[i + 1] - eoff[i]);
+    }
+    st.lz_encoded += ne;
+    st.delta_bytes += eoff[ne];
+    return true;
+}
+
+// what the bookkeeping needs of the commit run
+void CAGCCompressor::Impl::build_commit(BatchState &b, StoreFinish &f, CommitData &cdta)
+{
     cdta.ctgs = b.ctgs;
-    cdta.placed = &placed;
-    cdta.commit_upto = commit_upto;
+    cdta.placed = &placed_buf;
+    cdta.commit_upto = b.commit_upto;
     cdta.sample_from = b.s_from;
-    cdta.per_sample = std::move(per_sample);
-    cdta.new_ref_items = std::move(new_ref_items);
-    cdta.raw_items = std::move(raw_items);
-    cdta.enc_items = std::move(enc_items);
+    cdta.per_sample = std::move(b.per_sample);
+    cdta.new_ref_items = std::move(b.sto.new_ref_items);
+    cdta.raw_items = std::move(b.sto.raw_items);
+    cdta.enc_items = std::move(b.sto.enc_items);
     cdta.repetitive = std::move(b.sto.repetitive);
-    cdta.fetched = &fetched;
+    cdta.fetched = &fetch_buf;
     cdta.fetched_off = std::move(b.sto.fetched_off);
     cdta.ref_slot = b.sto.ref_slot;
     cdta.ref_nr = b.sto.ref_nr;
     cdta.ref_pin = b.sto.ref_pin;
     b.sto.ref_slot = -1;
-    cdta.enc_ptr = std::move(enc_ptr);
-    cdta.enc_len = std::move(enc_len);
-    if (dist_world > 1) {
-        if (!make_record_body(cdta))
-            return false;
-        LAP("record body");
-        if (dist_rank != dist_writer)
-            return true; // the writer rank does the bookkeeping from the record
-    }
-    if (hand_over) {
-        // beside the next sample: the registration's buffers change places with the second set, which is the task's until it is
-        // done (the raw pointers of cdta stay valid: the blocks themselves do not move)
-        std::unique_ptr<BookTask> t(new BookTask());
-        t->ctgs = *b.ctgs;
-        placed_buf.swap(placed_alt);
-        fetch_buf.swap(fetch_alt);
-        enc_buf.swap(enc_alt);
-        enc_buf2.swap(enc_alt2);
-        t->cd = std::move(cdta);
-        t->cd.ctgs = &t->ctgs;
-        t->cd.placed = &placed_alt;
-        t->cd.fetched = &fetch_alt;
-        if (!enc_later.empty()) {
-            t->enc_pending = true;
-            if (bulk && early_done) { // the deltas are in enc_buf (enc_alt since the swap above) already
-                if (early_enc.eoff.size() != enc_later.size() + 1) {
-                    err("internal: early collection of the encode does not match the registration");
-                    return false;
-                }
-                t->enc_pending = false;
-                t->enc_collected = true;
-                t->enc_eoff.swap(early_enc.eoff);
+    cdta.enc_ptr = std::move(f.enc_ptr);
+    cdta.enc_len = std::move(f.enc_len);
+}
+
+// the books beside the next sample: the registration's buffers change places with the second set, which is the task's until it is
+// done (the raw pointers of cdta stay valid: the blocks themselves do not move)
+bool CAGCCompressor::Impl::hand_over_books(BatchState &b, StoreFinish &f, CommitData &cdta)
+{
+    std::unique_ptr<BookTask> t(new BookTask());
+    t->ctgs = *b.ctgs;
+    placed_buf.swap(placed_alt);
+    fetch_buf.swap(fetch_alt);
+    enc_buf.swap(enc_alt);
+    enc_buf2.swap(enc_alt2);
+    t->cd = std::move(cdta);
+    t->cd.ctgs = &t->ctgs;
+    t->cd.placed = &placed_alt;
+    t->cd.fetched = &fetch_alt;
+    if (!f.enc_later.empty()) {
+        t->enc_pending = true;
+        if (f.bulk && f.early_done) { // the deltas are in enc_buf (enc_alt since the swap above) already
+            if (early_enc.eoff.size() != f.enc_later.size() + 1) {
+                err("internal: early collection of the encode does not match the registration");
+                return false;
             }
-            t->enc_todo = std::move(enc_later);
-            t->enc_text = enc_later_text;
-            // (the deltas encoded at commit time sit in enc_alt2 now; the device-launched encode of the whole sample is collected
-            // into the other buffer of the set, which holds nothing in this mode: spec_bytes == 0)
-            t->enc_dst = bulk ? &enc_alt : &enc_alt2;
+            t->enc_pending = false;
+            t->enc_collected = true;
+            t->enc_eoff.swap(early_enc.eoff);
         }
-        if (!enc_later2.empty()) {
-            t->enc2_pending = true;
-            t->enc2_todo = std::move(enc_later2);
-            t->enc2_text = enc_later2_text;
-            t->enc2_dst = &enc_alt2;
-        }
-        last_own_seq = book_submit(std::move(t));
-        LAP("book_and_store (queued)");
-        return true;
+        t->enc_todo = std::move(f.enc_later);
+        t->enc_text = f.enc_later_text;
+        // (the deltas encoded at commit time sit in enc_alt2 now; the device-launched encode of the whole sample is collected
+        // into the other buffer of the set, which holds nothing in this mode: spec_bytes == 0)
+        t->enc_dst = f.bulk ? &enc_alt : &enc_alt2;
     }
-    const bool ok = book_wait() && finish_ref_store(cdta, fetch_buf) && book_and_store(cdta);
-    LAP("book_and_store");
-    return ok;
+    if (!f.enc_later2.empty()) {
+        t->enc2_pending = true;
+        t->enc2_todo = std::move(f.enc_later2);
+        t->enc2_text = f.enc_later2_text;
+        t->enc2_dst = &enc_alt2;
+    }
+    last_own_seq = book_submit(std::move(t));
+    lap(b, "book_and_store (queued)");
+    return true;
 }
 
 // the second half of agc_hip_ref_store_begin_packed: waits for the slot, applies the reference's double-precision test to the lag
@@ -2811,22 +2757,7 @@ bool CAGCCompressor::Impl::finish_ref_store(CommitData &cd, bytes_t &fetched_dst
     cd.ref_slot = -1;
     const size_t nr = cd.ref_nr, cnt_bytes = nr * 28 * 4;
     const uint32_t *lag_cnt = (const uint32_t *)cd.ref_pin->data(), *lag_cur = (const uint32_t *)(cd.ref_pin->data() + cnt_bytes);
-    cd.repetitive.assign(nr, 0);
-    for (size_t fi = 0; fi < nr; ++fi) {
-        double best_frac = 0.0;
-        for (uint32_t l = 0; l < 28; ++l) {
-            const uint32_t cnt = lag_cnt[fi * 28 + l], cur = lag_cur[fi * 28 + l];
-            double frac = 0.0;
-            if (cur)
-                frac = (double)cnt / cur;
-            if (frac > best_frac) {
-                best_frac = frac;
-                if (best_frac >= 0.5)
-                    break;
-            }
-        }
-        cd.repetitive[fi] = !(best_frac < 0.5);
-    }
+    repetitive_from_lags(lag_cnt, lag_cur, nr, cd.repetitive);
     const uint64_t tot = cd.fetched_off.empty() ? 0 : cd.fetched_off.back();
     fetched_dst.assign(cd.ref_pin->data() + 2 * cnt_bytes, cd.ref_pin->data() + 2 * cnt_bytes + tot);
     cd.fetched = &fetched_dst;

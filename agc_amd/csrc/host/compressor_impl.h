@@ -944,6 +944,21 @@ struct CAGCCompressor::Impl {
     // classifies all contigs (one or several consecutive samples) against the current state and commits the
     // leading samples whose classification is certainly valid; n_committed = number of samples done
     bool process_batch(std::vector<Contig> &ctgs, const uint8_t *d_base, const std::vector<bytes_t> *host_data, uint32_t &n_committed);
+    struct EncodeJobs { // slices of the sample and the group each goes against, as the batched device calls take them; tot: their symbols
+        std::vector<uint32_t> gid, len;
+        std::vector<uint64_t> off;
+        std::vector<uint8_t> rc;
+        uint64_t tot = 0;
+        uint32_t n() const { return (uint32_t)gid.size(); }
+        void add(uint32_t g, uint64_t o, uint32_t l, bool r)
+        {
+            gid.push_back(g);
+            off.push_back(o);
+            len.push_back(l);
+            rc.push_back((uint8_t)r);
+            tot += l;
+        }
+    };
     struct BatchState { // working set of one process_batch call
         std::vector<Contig> *ctgs = nullptr;
         const uint8_t *d_base = nullptr;           // one byte per symbol (nullptr when the sample came packed and nothing needed bytes)
@@ -959,7 +974,7 @@ struct CAGCCompressor::Impl {
         // would have to, it only says so (needs_turn) and the sample is prepared again at its turn
         bool no_new_splitters = false, needs_turn = false;
         // adaptive mode, device segments: the contigs without a splitter and what find_new_splitters made of them, handed to the
-        // host's scan when the set has to grow (stage_scan_dev -> stage_scan)
+        // host's scan when the set has to grow (stage_scan_dev -> stage_scan_host)
         bool mined_valid = false;
         std::vector<uint32_t> mined_need;
         std::vector<std::vector<uint64_t>> mined_found;
@@ -968,6 +983,17 @@ struct CAGCCompressor::Impl {
             uint32_t gid = 0, len = 0, enc_len = 0;
             int32_t pending = -1; // >= 0: the delta is result no. `pending` of the encode in flight on the device's second lane
             bool rc = false, valid = false;
+            void set(uint32_t g, uint64_t o, uint32_t l, bool r, uint64_t eo, uint32_t el, int32_t pend = -1)
+            {
+                valid = true;
+                gid = g;
+                off = o;
+                len = l;
+                rc = r;
+                enc_off = eo;
+                enc_len = el;
+                pending = pend;
+            }
         };
         std::vector<Spec> spec;
         uint64_t spec_bytes = 0;                   // bytes of enc_buf the speculative deltas occupy
@@ -981,9 +1007,8 @@ struct CAGCCompressor::Impl {
         bool known_launch_due = false; // the whole-sample encode has its descriptors on the device and is not launched yet (launch_known_encode)
         uint64_t known_text = 0;       // symbols of its texts
         uint64_t early_seq = 0; // != 0: the book thread's early task that collects that encode (Impl::early_enc takes its result)
-        std::vector<uint32_t> flight_keys, flight_gid, flight_len;
-        std::vector<uint64_t> flight_off;
-        std::vector<uint8_t> flight_rc;
+        std::vector<uint32_t> flight_keys; // the overlapped encode in flight (overlap_encode_begin / _end): Placed::key of its jobs
+        EncodeJobs flight;
         std::vector<uint64_t> changed;             // k-mers whose terminator list changed in the last commit run
         uint32_t commit_upto = 0;                  // registrations of the window that are committed now
         std::vector<uint32_t> order;               // committed items in registration order
@@ -1003,10 +1028,22 @@ struct CAGCCompressor::Impl {
             const PinnedBytes *ref_pin = nullptr;
         } sto;
     };
-    bool stage_scan(BatchState &b);
+    bool stage_scan(BatchState &b); // the device's segments where they can be had (stage_scan_dev), else stage_scan_host
+    bool stage_scan_host(BatchState &b);
     bool launch_known_encode(BatchState &b, bool launched_already = false);
     void finish_spec_fill(BatchState &b);
     int stage_scan_dev(BatchState &b);
+    // parts of the two scan paths
+    bool window_offsets(const BatchState &b, std::vector<uint64_t> &ctg_off);
+    bool mine_contigs(BatchState &b, const std::vector<uint32_t> &need, std::vector<std::vector<uint64_t>> &found);
+    void uncount_bases(BatchState &b, uint32_t from_ctg);
+    void wait_for_turn(BatchState &b);
+    void dev_segments_to_host(size_t n_segs, bool enc, std::vector<uint8_t> &is_known);
+    int mine_dev_window(BatchState &b, size_t n_segs);
+    bool extend_splitters(BatchState &b, const std::vector<uint64_t> &ctg_off, uint64_t &n_hits);
+    void merge_rescan_hits(const std::vector<uint8_t> &has_hit, uint64_t &n_hits, const std::vector<uint32_t> &c2, const std::vector<uint64_t> &p2,
+                           const std::vector<uint64_t> &d2, const std::vector<uint64_t> &r2, uint64_t n2);
+    void cut_segments(BatchState &b, uint64_t n_hits);
     bool use_dev_segments(const BatchState &b) const;
     // adaptive mode with windows of several registrations: only where the device delivers the segments (the cut of a window at
     // the registration that brings new splitters lives there)
@@ -1017,12 +1054,43 @@ struct CAGCCompressor::Impl {
     bool lane_inflight[2] = {false, false}; // (guarded by book_mtx) device lanes 0 / 1 (AGC_HIP_ENCODE_LANES)
     void lane2_acquire(int lane = 0);
     void lane2_release(int lane = 0);
+    struct MidJob { // a missing-middle candidate: the segment and the two groups its halves would go to
+        uint32_t seg, gid1, gid2;
+        uint8_t rc1, pf1, rc2, pf2;
+    };
+    struct Classify { // what crosses the parts of stage_classify
+        std::vector<Cand> cands;
+        std::vector<uint32_t> est_cost, est_peak; // per candidate
+        std::vector<MidJob> mids;
+    };
     bool stage_classify(BatchState &b);
+    bool classify_keys(BatchState &b, Classify &cl);
+    bool classify_estimates(BatchState &b, Classify &cl);
+    void classify_resolve(BatchState &b, Classify &cl);
+    bool classify_mids(BatchState &b, Classify &cl);
+    bool classify_split_points(BatchState &b, Classify &cl);
     bool stage_place(BatchState &b);
     bool stage_register(BatchState &b);
     bool stage_store(BatchState &b);
     bool stage_store_head(BatchState &b);
     bool stage_store_finish(BatchState &b);
+    struct StoreFinish { // what crosses the parts of stage_store_finish
+        bool hand_over = false, early_done = false, bulk = false;
+        std::vector<const uint8_t *> enc_ptr; // delta of every enc_items entry
+        std::vector<uint32_t> enc_len;
+        std::vector<uint32_t> enc_later;  // per result of the encode in flight on the second lane: its position in enc_items (~0u: unused)
+        std::vector<uint32_t> enc_later2; // ... and of the one launched on lane 1 while lane 0 still holds the whole-sample encode
+        uint64_t enc_later_text = 0, enc_later2_text = 0;
+    };
+    bool register_new_refs(BatchState &b);
+    bool collect_known_encode(BatchState &b, bool early_done);
+    bool encode_rest(BatchState &b, StoreFinish &f);
+    void build_commit(BatchState &b, StoreFinish &f, CommitData &cdta);
+    bool hand_over_books(BatchState &b, StoreFinish &f, CommitData &cdta);
+    // the encode-call layer: job list from placed items, the call with its grow-and-retry loop, the collection of a lane
+    EncodeJobs encode_jobs(const std::vector<uint32_t> &items, bool book = true);
+    bool encode_now(BatchState &b, const EncodeJobs &jobs, PinnedBytes &dst, uint64_t base, uint64_t first_cap, std::vector<uint64_t> &eoff);
+    bool collect_lane(int lane, PinnedBytes &dst, uint64_t base, uint64_t first_cap, size_t ne, std::vector<uint64_t> &eoff);
     bool spec_encode(BatchState &b);
     bool overlap_encode_begin(BatchState &b);
     bool overlap_encode_end(BatchState &b);

@@ -414,7 +414,7 @@ def test_samples_in_the_packed_layout_give_the_reference_archive(cli, name, over
     assert hashlib.sha256(got).hexdigest() == GOLD[name]["sha256"]
 
 
-@pytest.mark.parametrize("name", ["syn_mixed", "syn_c4_twin"])
+@pytest.mark.parametrize("name", ["syn_mixed", "syn_c4_twin", "syn_adaptive", "syn_c5_twin"])
 def test_segments_from_the_device_or_cut_on_the_host_give_the_same_archive(cli, name, tmp_path, monkeypatch):
     """Single-registration windows take their segments, keys and group look-ups from the device (agc_hip_segments_packed; the
     encode of the segments whose group is known is launched there too) -- the laps say so; AGC_AMD_DEV_SEGMENTS=0 (hits to the
