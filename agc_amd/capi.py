@@ -558,6 +558,24 @@ class Context:
     def ref_lag_counts_packed(self, pk, off, length, rc=None):
         return self._lag(self.L.agc_hip_ref_lag_counts_packed, C.byref(pk), off, length, rc)
 
+    def ref_store_begin_packed(self, slot, n_refs, pk, off, length, rc=None):
+        """lag counts of the first n_refs slices and the symbols of all of them, queued on the reference-store stream"""
+        o, l = _a(off, np.uint64), _a(length, np.uint32)
+        r = _a(rc, np.uint8) if rc is not None else None
+        cap = int(l.astype(np.uint64).sum())
+        cnt, cur = np.zeros((n_refs, 28), np.uint32), np.zeros((n_refs, 28), np.uint32)
+        out, ooff = np.empty(cap, np.uint8), np.zeros(o.size + 1, np.uint64)
+        if not hasattr(self, "_ref_store_pending"):
+            self._ref_store_pending = {}
+        self._ref_store_pending[slot] = (cnt, cur, out, ooff, o, l, r)  # (the device writes the first three until the end call)
+        self._chk(self.L.agc_hip_ref_store_begin_packed(self.h, slot, n_refs, o.size, C.byref(pk), _p(o, u64p), _p(l, u32p), _p(r, vp), _p(cnt, vp), _p(cur, vp),
+                                                        _p(out, vp), cap, _p(ooff, u64p)))
+
+    def ref_store_end(self, slot):
+        """waits for the slot: -> (cnt, cur, out bytes, out_off[n+1])"""
+        self._chk(self.L.agc_hip_ref_store_end(self.h, slot))
+        return self._ref_store_pending.pop(slot)[:4]
+
     def lz_encode_end(self, enc_cap=None):
         """second half: waits, -> (enc bytes, enc_off[n+1]) exactly as lz_encode_batch_dev"""
         g, o, l, r = self._enc_pending

@@ -356,6 +356,28 @@ struct KTimer {
     }
 };
 
+// host time between the marks of a call with many items (n > 10000), on stderr under AGC_HIP_LAPS
+struct Laps {
+    const char *who;
+    bool on;
+    double last = 0;
+    static bool enabled()
+    {
+        static const bool e = getenv("AGC_HIP_LAPS") != nullptr;
+        return e;
+    }
+    static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    Laps(const char *who_, uint32_t n) : who(who_), on(enabled() && n > 10000) { last = on ? now() : 0; }
+    void operator()(const char *what)
+    {
+        if (!on)
+            return;
+        const double t = now();
+        fprintf(stderr, "    %s lap %s %.3f ms\n", who, what, t - last);
+        last = t;
+    }
+};
+
 // the entropy stage's kernels: own events, own stream (only that call writes ms[AGC_HIP_K_ZSTD])
 struct ZTimer {
     agc_hip_ctx *c;
@@ -379,24 +401,9 @@ struct ZTimer {
 
 int ensure_z(agc_hip_ctx *c, DevBuf &b, size_t bytes) { return ensure(c, b, bytes, c->zstream); }
 
-// host -> device, without the calling thread waiting: through the context's pinned ring (a slot is reused a ring's length later:
-// tens of steps; the wrap waits for the LZ streams once to be sure).  Large copies go the ordinary way.
-int upload(agc_hip_ctx *c, void *d_dst, const void *h_src, size_t bytes, hipStream_t st)
+// one piece of an upload (at most half a part of the ring): copied into the ring, the copy to the device queued on `st` from there
+int upload_piece(agc_hip_ctx *c, void *d_dst, const void *h_src, size_t bytes, hipStream_t st, size_t RING, size_t PART)
 {
-    // (AGC_HIP_UPLOAD_RING_MB: a smaller ring for the tests -- the head then comes back to a part, and waits for its events, many
-    // times in a small archive; a piece is at most half a part)
-    static const size_t RING = [] {
-        const char *e = getenv("AGC_HIP_UPLOAD_RING_MB");
-        const long mb = e ? atol(e) : 64;
-        return (size_t)(mb < 1 ? 1 : mb > 64 ? 64 : mb) << 20;
-    }();
-    const size_t PART = RING / agc_hip_ctx::UP_PARTS, MAX_PIECE = std::min<size_t>((size_t)8 << 20, PART / 2);
-    if (!bytes)
-        return AGC_HIP_OK;
-    if (bytes > MAX_PIECE) {
-        HIPCHK(c, hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, st));
-        return AGC_HIP_OK;
-    }
     // (the lock is held until the copy is queued: the event a part records on a stream when the head leaves is then behind every
     // copy out of that part)
     std::lock_guard<std::mutex> lk(c->up_mtx);
@@ -440,6 +447,25 @@ int upload(agc_hip_ctx *c, void *d_dst, const void *h_src, size_t bytes, hipStre
     return AGC_HIP_OK;
 }
 
+// host -> device on `st`, without the calling thread waiting for the copy engine (a copy from pageable memory would make it wait).
+// THE CONTRACT: when upload() returns, the caller may free or overwrite h_src.  Every byte goes through the context's pinned ring,
+// in pieces of at most MAX_PIECE, and the device copies are queued out of the ring; a slot is reused a ring's length later (tens
+// of steps), after the head has waited for the events of the part it comes back to.
+int upload(agc_hip_ctx *c, void *d_dst, const void *h_src, size_t bytes, hipStream_t st)
+{
+    // (AGC_HIP_UPLOAD_RING_MB: a smaller ring for the tests -- the head then comes back to a part, and waits for its events, many
+    // times in a small archive; a piece is at most half a part)
+    static const size_t RING = [] {
+        const char *e = getenv("AGC_HIP_UPLOAD_RING_MB");
+        const long mb = e ? atol(e) : 64;
+        return (size_t)(mb < 1 ? 1 : mb > 64 ? 64 : mb) << 20;
+    }();
+    const size_t PART = RING / agc_hip_ctx::UP_PARTS, MAX_PIECE = std::min<size_t>((size_t)8 << 20, PART / 2);
+    for (size_t o = 0; o < bytes; o += MAX_PIECE)
+        CHK(upload_piece(c, (uint8_t *)d_dst + o, (const uint8_t *)h_src + o, std::min(bytes - o, MAX_PIECE), st, RING, PART));
+    return AGC_HIP_OK;
+}
+
 // the entropy stage's stream yields to the streams of the steps wherever the hardware queues let it
 hipError_t create_low_priority_stream(hipStream_t *s)
 {
@@ -468,11 +494,8 @@ int upload_refs(agc_hip_ctx *c)
         lo = 0;
         hi = c->refs.size();
     }
-    if (hi > lo) {
+    if (hi > lo)
         CHK(upload(c, (RefDesc *)c->d_refs.p + lo, c->refs.data() + lo, (hi - lo) * sizeof(RefDesc), c->stream));
-        if ((hi - lo) * sizeof(RefDesc) > ((size_t)8 << 20))
-            HIPCHK(c, hipStreamSynchronize(c->stream)); // (beyond upload()'s staging: the vector may be reallocated by the next register)
-    }
     c->refs_on_dev = c->refs.size();
     c->refs_dirty = false;
     c->refs_dirty_lo = c->refs_dirty_hi = 0;
@@ -510,27 +533,49 @@ int pack_bytes(agc_hip_ctx *c, const uint8_t *d_codes, uint64_t n, PackTemp &t, 
     return AGC_HIP_OK;
 }
 
-// the sequences [h_off[i], h_off[i] + h_len[i]) of a byte buffer: the range they span is packed, off2 = their offsets in it
-int pack_range(agc_hip_ctx *c, const uint8_t *d_base, uint32_t n, const uint64_t *h_off, const uint32_t *h_len, PackTemp &t, hipStream_t st,
-               PackedSrc &out, std::vector<uint64_t> &off2)
+// What every byte-input entry point does once its arguments are checked: the range its sequences [h_off[i], h_off[i] + h_len[i])
+// span is packed into `t` on `st`, and `then(src, off2)` -- the work of the packed entry point of the same name -- runs on that
+// copy, off2 = their offsets in it
+template <class F>
+int with_packed_bytes(agc_hip_ctx *c, const uint8_t *d_base, uint32_t n, const uint64_t *h_off, const uint32_t *h_len, PackTemp &t, hipStream_t st, F then)
 {
+    HIPCHK(c, hipSetDevice(c->device));
     uint64_t lo = ~0ULL, hi = 0;
     for (uint32_t i = 0; i < n; ++i)
         if (h_len[i]) {
             lo = std::min<uint64_t>(lo, h_off[i]);
             hi = std::max<uint64_t>(hi, h_off[i] + h_len[i]);
         }
-    off2.assign(n, 0);
-    if (hi <= lo) {
-        out = PackedSrc();
-        return AGC_HIP_OK;
+    PackedSrc src;
+    std::vector<uint64_t> off2(n, 0);
+    if (hi > lo) {
+        for (uint32_t i = 0; i < n; ++i)
+            off2[i] = h_len[i] ? h_off[i] - lo : 0;
+        CHK(pack_bytes(c, d_base + lo, hi - lo, t, st, src));
     }
-    for (uint32_t i = 0; i < n; ++i)
-        off2[i] = h_len[i] ? h_off[i] - lo : 0;
-    return pack_bytes(c, d_base + lo, hi - lo, t, st, out);
+    return then(src, off2.data());
 }
 
-PackedSrc src_of(const agc_hip_packed *pk) 
+// ... and every host-text entry point: the texts go to d_in back to back (16-byte aligned; h_text is the caller's, and every entry
+// point waits for the stream before it returns), `then(d_base, doff)` is the byte-input entry point of the same name
+template <class F>
+int with_host_texts(agc_hip_ctx *c, uint32_t n, const uint8_t *h_text, const uint64_t *h_off, const uint32_t *h_len, F then)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<uint64_t> doff(n);
+    size_t tot = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        doff[i] = tot;
+        tot += ((size_t)h_len[i] + 15) & ~(size_t)15;
+    }
+    CHK(ensure(c, c->d_in, tot + 64));
+    for (uint32_t i = 0; i < n; ++i)
+        if (h_len[i])
+            HIPCHK(c, hipMemcpyAsync((uint8_t *)c->d_in.p + doff[i], h_text + h_off[i], h_len[i], hipMemcpyHostToDevice, c->stream));
+    return then((const uint8_t *)c->d_in.p, doff.data());
+}
+
+PackedSrc src_of(const agc_hip_packed *pk)
 {
     PackedSrc s;
     s.words = pk->d_words;
@@ -546,6 +591,62 @@ bool slices_inside(const PackedSrc &src, uint32_t n, const uint64_t *h_off, cons
         if (h_len[i] && (h_off[i] > src.n_symbols || h_len[i] > src.n_symbols - h_off[i]))
             return false;
     return true;
+}
+
+// Slice jobs (ViewJob) run out of the first stream's buffers or out of those of a reference-store slot.  The three helpers below
+// queue on `st` and wait for nothing; `which` is the launch's timing row (KTimer; < 0: not timed).
+struct SliceBufs {
+    DevBuf &slices, &out, &lag;
+};
+SliceBufs slice_bufs(agc_hip_ctx *c) { return {c->d_slices, c->d_compact, c->d_lag}; }
+SliceBufs slice_bufs(agc_hip_ctx::RefStore &r) { return {r.d_slices, r.d_out, r.d_lag}; }
+
+// the jobs of n slices of `src` in b.slices: slice i goes to b.out + h_out_off[i] (h_out_off[n] bytes in all), or nowhere when
+// h_out_off is nullptr (counted only)
+int put_view_jobs(agc_hip_ctx *c, SliceBufs b, hipStream_t st, uint32_t n, const PackedSrc &src, const uint64_t *h_off, const uint32_t *h_len, const uint8_t *h_rc,
+                  const uint64_t *h_out_off)
+{
+    if (!slices_inside(src, n, h_off, h_len))
+        return AGC_HIP_EINVAL;
+    if (h_out_off)
+        CHK(ensure(c, b.out, h_out_off[n] + 64, st));
+    CHK(ensure(c, b.slices, (size_t)n * sizeof(ViewJob), st));
+    std::vector<ViewJob> sl(n);
+    for (uint32_t i = 0; i < n; ++i)
+        sl[i] = {{src.words, src.esc_index, src.esc_bytes, h_off[i], h_len[i], h_rc ? (uint32_t)(h_rc[i] != 0) : 0u},
+                 h_out_off ? (uint8_t *)b.out.p + h_out_off[i] : nullptr};
+    return upload(c, b.slices.p, sl.data(), (size_t)n * sizeof(ViewJob), st);
+}
+
+// the repetitiveness counters of the first n jobs in b.slices (n > 0), 28 + 28 words each, to h_cnt and h_cur
+int queue_lag_counts(agc_hip_ctx *c, SliceBufs b, hipStream_t st, uint32_t n, uint32_t *h_cnt, uint32_t *h_cur, int which)
+{
+    const size_t half = (size_t)n * 28 * 4;
+    CHK(ensure(c, b.lag, 2 * half, st));
+    uint32_t *d_cnt = (uint32_t *)b.lag.p, *d_cur = d_cnt + (size_t)n * 28;
+    // few slices (steady state): each spread over several blocks to fill the chip
+    const uint32_t split = n >= 2048 ? 1u : std::min<uint32_t>(32u, 2048u / n);
+    HIPCHK(c, hipMemsetAsync(b.lag.p, 0, 2 * half, st));
+    {
+        KTimer t(c, which);
+        hipLaunchKernelGGL(lag_counts_kernel, dim3(n * split), dim3(256), 0, st, (const ViewJob *)b.slices.p, d_cnt, d_cur, split);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_cnt, d_cnt, half, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(h_cur, d_cur, half, hipMemcpyDeviceToHost, st));
+    return AGC_HIP_OK;
+}
+
+// the symbols of the n jobs in b.slices, one byte each, into b.out and from there to h_out (tot bytes)
+int queue_expand(agc_hip_ctx *c, SliceBufs b, hipStream_t st, uint32_t n, uint8_t *h_out, uint64_t tot, int which)
+{
+    {
+        KTimer t(c, which);
+        hipLaunchKernelGGL(slice_expand_kernel, dim3(grid_for(n, 1, 65536)), dim3(256), 0, st, (const ViewJob *)b.slices.p, n);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_out, b.out.p, tot, hipMemcpyDeviceToHost, st));
+    return AGC_HIP_OK;
 }
 
 } // namespace
@@ -893,10 +994,10 @@ static int splitters_upload(agc_hip_ctx *c)
     CHK(ensure(c, c->d_table, cap * 8));
     CHK(ensure(c, c->d_bloom, BLOOM_WORDS * 4));
     CHK(ensure(c, c->d_bloom2, BLOOM2_WORDS * 4));
-    HIPCHK(c, hipMemcpyAsync(c->d_bloom2.p, bloom2.data(), BLOOM2_WORDS * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_table.p, tab.data(), cap * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_bloom.p, bloom.data(), BLOOM_WORDS * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    CHK(upload(c, c->d_bloom2.p, bloom2.data(), BLOOM2_WORDS * 4, c->stream));
+    CHK(upload(c, c->d_table.p, tab.data(), cap * 8, c->stream));
+    CHK(upload(c, c->d_bloom.p, bloom.data(), BLOOM_WORDS * 4, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (the prefetch stream scans with these tables too, ordered behind nothing but this)
     c->table_mask = cap - 1;
     return AGC_HIP_OK;
 }
@@ -1347,8 +1448,8 @@ static int sbloom_upload(agc_hip_ctx *c, uint32_t k)
         }
     }
     CHK(ensure(c, c->d_sbloom, SBLOOM_WORDS * 4));
-    HIPCHK(c, hipMemcpyAsync(c->d_sbloom.p, bl.data(), SBLOOM_WORDS * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    CHK(upload(c, c->d_sbloom.p, bl.data(), SBLOOM_WORDS * 4, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (as in splitters_upload: the prefetch stream reads the filter)
     c->sbloom_k = k;
     c->sbloom_n = c->spl.size();
     return AGC_HIP_OK;
@@ -1499,7 +1600,6 @@ int agc_hip_prefetch_packed_dev(agc_hip_ctx *c, const agc_hip_packed *pk, const 
         CHK(ensure(c, pf.d_counter, 64, pf.stream));
         pf.dev_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(total / 1000 + 4096, pf.d_hits.cap / sizeof(ScanHit)), 1u << 30);
         CHK(ensure(c, pf.d_hits, (size_t)pf.dev_cap * sizeof(ScanHit), pf.stream));
-        // (the ranges go through a pageable vector: the copy is staged by the runtime before the call returns)
         CHK(upload(c, pf.d_ranges.p, ranges.data(), ranges.size() * sizeof(ScanRange), pf.stream));
         HIPCHK(c, hipMemsetAsync(pf.d_counter.p, 0, 4, pf.stream));
         if (!c->lds_scan_set) {
@@ -1752,11 +1852,9 @@ int agc_hip_ref_register_batch_dev(agc_hip_ctx *c, uint32_t n_refs, const uint32
         return AGC_HIP_EINVAL;
     if (!n_refs)
         return AGC_HIP_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    PackedSrc src;
-    std::vector<uint64_t> off2;
-    CHK(pack_range(c, d_base, n_refs, h_off, h_len, c->pk1, c->stream, src, off2));
-    return ref_register_impl(c, n_refs, h_gid, src, off2.data(), h_len, h_rc, min_match_len);
+    return with_packed_bytes(c, d_base, n_refs, h_off, h_len, c->pk1, c->stream, [&](const PackedSrc &src, const uint64_t *off2) {
+        return ref_register_impl(c, n_refs, h_gid, src, off2, h_len, h_rc, min_match_len);
+    });
 }
 
 int agc_hip_ref_register(agc_hip_ctx *c, uint32_t gid, const uint8_t *h_ref, uint32_t n, uint32_t min_match_len)
@@ -1784,13 +1882,11 @@ int agc_hip_ref_get(agc_hip_ctx *c, uint32_t gid, uint8_t *h_ref, uint32_t cap, 
     if (cap < r.ref_size)
         return AGC_HIP_ECAP;
     if (r.ref_size) { // the stored 2-bit form back as one byte per symbol
-        CHK(ensure(c, c->d_compact, (size_t)r.ref_size + 64));
-        const ViewJob vj = {{r.words, r.esc_index, r.esc_bytes, 0, r.ref_size, 0}, c->d_compact.p};
-        CHK(ensure(c, c->d_slices, sizeof(ViewJob)));
-        HIPCHK(c, hipMemcpyAsync(c->d_slices.p, &vj, sizeof(ViewJob), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(slice_expand_kernel, dim3(1), dim3(256), 0, c->stream, (const ViewJob *)c->d_slices.p, 1u);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(h_ref, c->d_compact.p, r.ref_size, hipMemcpyDeviceToHost, c->stream));
+        const SliceBufs B = slice_bufs(c);
+        const PackedSrc stored = {r.words, r.esc_index, r.esc_bytes, r.ref_size};
+        const uint64_t off = 0, out_off[2] = {0, r.ref_size};
+        CHK(put_view_jobs(c, B, c->stream, 1, stored, &off, &r.ref_size, nullptr, out_off));
+        CHK(queue_expand(c, B, c->stream, 1, h_ref, r.ref_size, -1));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return AGC_HIP_OK;
@@ -1845,16 +1941,7 @@ int prepare_batch(agc_hip_ctx *c, int mode, uint32_t n, const uint32_t *h_gid, c
     DevBuf &L_segs = lane ? c->lane(lane).d_segs : c->d_segs, &L_counter = lane ? c->lane(lane).d_counter : c->d_counter,
            &L_resv = lane ? c->lane(lane).d_resv : c->d_resv, &L_resp = lane ? c->lane(lane).d_resp : c->d_resp;
     const hipStream_t L_stream = lane ? c->lane(lane).s : c->stream;
-    static const bool laps = getenv("AGC_HIP_LAPS") != nullptr;
-    auto tnow = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double lt = laps ? tnow() : 0;
-    auto LAP = [&](const char *what) {
-        if (laps && n > 10000) {
-            const double t = tnow();
-            fprintf(stderr, "    prepare_batch lap %s %.3f ms\n", what, t - lt);
-            lt = t;
-        }
-    };
+    Laps LAP("prepare_batch", n);
     for (uint32_t i = 0; i < n; ++i)
         if (h_gid[i] >= c->refs.size() || !c->refs[h_gid[i]].valid) {
             c->err = "group " + std::to_string(h_gid[i]) + " has no registered reference";
@@ -1889,7 +1976,7 @@ int prepare_batch(agc_hip_ctx *c, int mode, uint32_t n, const uint32_t *h_gid, c
             std::memcpy(order.data(), src, (size_t)n * 4);
     }
     LAP("sort");
-    if (laps && mode == MODE_COSTVEC && n) {
+    if (Laps::enabled() && mode == MODE_COSTVEC && n) {
         uint64_t tot = 0;
         for (uint32_t i = 0; i < n; ++i)
             tot += h_len[i];
@@ -1942,7 +2029,7 @@ int prepare_batch(agc_hip_ctx *c, int mode, uint32_t n, const uint32_t *h_gid, c
             KTimer t(c, AGC_HIP_K_FILTER);
             hipLaunchKernelGGL(key_filter_kernel, dim3((uint32_t)fjobs.size()), dim3(FILTER_THREADS), 0, L_stream, (const FilterJob *)c->d_fjobs.p);
         }
-        HIPCHK(c, hipGetLastError()); // (fjobs is a local: upload() took its copy)
+        HIPCHK(c, hipGetLastError());
     }
     LAP("descriptors");
     CHK(ensure(c, L_segs, (size_t)n * sizeof(SegDesc), L_stream));
@@ -2015,11 +2102,8 @@ int launch_parse(agc_hip_ctx *c, uint32_t n, uint8_t *out_bytes, uint32_t *out_u
             CHK(ensure(c, cb.d_logn, jobs.size() * 4, st));
             if (MODE == MODE_ENCODE)
                 CHK(ensure(c, cb.d_out, jobs.size() * (size_t)pl.chunk_stride + 64, st));
-            // (the two lists go through the pinned ring in pieces: a window of diverged genomes has a few 10 k chunks)
-            for (size_t o = 0; o < jobs.size(); o += 1u << 19)
-                CHK(upload(c, (ChunkJob *)cb.d_jobs.p + o, jobs.data() + o, std::min<size_t>(jobs.size() - o, 1u << 19) * sizeof(ChunkJob), st));
-            for (size_t o = 0; o < seg0.size(); o += 1u << 20)
-                CHK(upload(c, (uint32_t *)cb.d_seg0.p + o, seg0.data() + o, std::min<size_t>(seg0.size() - o, 1u << 20) * 4, st));
+            CHK(upload(c, cb.d_jobs.p, jobs.data(), jobs.size() * sizeof(ChunkJob), st)); // (a window of diverged genomes has a few 10 k chunks)
+            CHK(upload(c, cb.d_seg0.p, seg0.data(), seg0.size() * 4, st));
             pl.jobs = (const ChunkJob *)cb.d_jobs.p;
             pl.seg_chunk0 = (const uint32_t *)cb.d_seg0.p;
             pl.logs = (ChunkState *)cb.d_logs.p;
@@ -2122,27 +2206,48 @@ int launch_parse(agc_hip_ctx *c, uint32_t n, uint8_t *out_bytes, uint32_t *out_u
     return AGC_HIP_OK;
 }
 
-int stage_host_texts(agc_hip_ctx *c, uint32_t n, const uint8_t *h_text, const uint64_t *h_off, const uint32_t *h_len,
-                     std::vector<uint64_t> &doff)
+// The deltas of a parsed batch, back to back on the host: offsets from their lengths, one gather, one copy, waited for on `st`.
+// `b`: the buffers of the stream that parsed (the first stream's or a lane's).  direct: a pinned h_enc (agc_hip_host_alloc) is
+// written by the gather itself, over the link -- no second buffer, no copy engine; anything else, and every result of the one-call
+// encode, gets the deltas compacted in HBM and copied.
+struct EncBufs {
+    DevBuf &scratch, &segs, &resv, &dstoff, &compact;
+};
+
+int collect_deltas(agc_hip_ctx *c, EncBufs b, hipStream_t st, uint32_t n, const uint32_t *lens, bool direct, uint8_t *h_enc, uint64_t enc_cap, uint64_t *h_enc_off,
+                   Laps LAP)
 {
-    doff.resize(n);
-    size_t tot = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        doff[i] = tot;
-        tot += ((size_t)h_len[i] + 15) & ~(size_t)15;
-    }
-    CHK(ensure(c, c->d_in, tot + 64));
     for (uint32_t i = 0; i < n; ++i)
-        if (h_len[i])
-            HIPCHK(c, hipMemcpyAsync((uint8_t *)c->d_in.p + doff[i], h_text + h_off[i], h_len[i], hipMemcpyHostToDevice, c->stream));
+        h_enc_off[i + 1] = h_enc_off[i] + lens[i];
+    const uint64_t tot = h_enc_off[n];
+    if (tot > enc_cap)
+        return AGC_HIP_ECAP;
+    LAP("offsets");
+    if (!tot)
+        return AGC_HIP_OK;
+    if (!h_enc)
+        return AGC_HIP_EINVAL;
+    CHK(ensure(c, b.dstoff, (size_t)n * 8, st));
+    CHK(upload(c, b.dstoff.p, h_enc_off, (size_t)n * 8, st));
+    void *d_host = nullptr;
+    if (direct && hipHostGetDevicePointer(&d_host, h_enc, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        d_host = nullptr;
+    }
+    if (!d_host)
+        CHK(ensure(c, b.compact, tot, st));
+    hipLaunchKernelGGL(gather_bytes_kernel, dim3(grid_for(n, 1, 8192)), dim3(256), 0, st, (const uint8_t *)b.scratch.p, (const SegDesc *)b.segs.p,
+                       (const uint32_t *)b.resv.p, (const uint64_t *)b.dstoff.p, n, d_host ? (uint8_t *)d_host : (uint8_t *)b.compact.p);
+    HIPCHK(c, hipGetLastError());
+    if (!d_host)
+        HIPCHK(c, hipMemcpyAsync(h_enc, b.compact.p, tot, hipMemcpyDeviceToHost, st));
+    LAP("queued");
+    HIPCHK(c, hipStreamSynchronize(st));
+    LAP("deltas on the host");
     return AGC_HIP_OK;
 }
 
 } // namespace
-
-extern "C" {
-
-} // extern "C"
 
 static int lz_encode_impl(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const PackedSrc &src, const uint64_t *h_off, const uint32_t *h_len,
                           const uint8_t *h_rc, uint8_t *h_enc, uint64_t enc_cap, uint64_t *h_enc_off)
@@ -2154,25 +2259,8 @@ static int lz_encode_impl(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, con
     std::vector<uint32_t> lens(n);
     HIPCHK(c, hipMemcpyAsync(lens.data(), c->d_resv.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (uint32_t i = 0; i < n; ++i)
-        h_enc_off[i + 1] = h_enc_off[i] + lens[i];
-    const uint64_t tot = h_enc_off[n];
-    if (tot > enc_cap)
-        return AGC_HIP_ECAP;
-    if (!tot)
-        return AGC_HIP_OK;
-    if (!h_enc)
-        return AGC_HIP_EINVAL;
-    CHK(ensure(c, c->d_dstoff, (size_t)n * 8));
-    CHK(ensure(c, c->d_compact, tot));
-    CHK(upload(c, c->d_dstoff.p, h_enc_off, (size_t)n * 8, c->stream));
-    hipLaunchKernelGGL(gather_bytes_kernel, dim3(grid_for(n, 1, 8192)), dim3(256), 0, c->stream, (const uint8_t *)c->d_scratch.p,
-                       (const SegDesc *)c->d_segs.p, (const uint32_t *)c->d_resv.p, (const uint64_t *)c->d_dstoff.p, n,
-                       (uint8_t *)c->d_compact.p);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(h_enc, c->d_compact.p, tot, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return AGC_HIP_OK;
+    return collect_deltas(c, {c->d_scratch, c->d_segs, c->d_resv, c->d_dstoff, c->d_compact}, c->stream, n, lens.data(), false, h_enc, enc_cap, h_enc_off,
+                          Laps("", 0));
 }
 
 // The encode in two halves (include/agc_hip.h): begin queues the parse and the copy of the delta lengths on the context's second
@@ -2182,7 +2270,7 @@ static int lz_encode_begin_impl(agc_hip_ctx *c, int lane, uint32_t n, const uint
                                 const uint32_t *h_len, const uint8_t *h_rc)
 {
     agc_hip_ctx::Lane2 &L = c->lane(lane);
-    static thread_local Batch b; // (its descriptors are read by an asynchronous upload: they outlive this call)
+    Batch b;
     CHK(prepare_batch(c, MODE_ENCODE, n, h_gid, src, h_off, h_len, h_rc, nullptr, b, lane));
     CHK(ensure(c, L.d_scratch, b.out_total + 64, L.s));
     if (L.h_lens_cap < n) {
@@ -2252,11 +2340,9 @@ int agc_hip_lz_encode_batch_dev(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gi
     h_enc_off[0] = 0;
     if (!n)
         return AGC_HIP_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    PackedSrc src;
-    std::vector<uint64_t> off2;
-    CHK(pack_range(c, d_base, n, h_off, h_len, c->pk1, c->stream, src, off2));
-    return lz_encode_impl(c, n, h_gid, src, off2.data(), h_len, h_rc, h_enc, enc_cap, h_enc_off);
+    return with_packed_bytes(c, d_base, n, h_off, h_len, c->pk1, c->stream, [&](const PackedSrc &src, const uint64_t *off2) {
+        return lz_encode_impl(c, n, h_gid, src, off2, h_len, h_rc, h_enc, enc_cap, h_enc_off);
+    });
 }
 
 int agc_hip_lz_encode_begin_packed_on(agc_hip_ctx *c, uint32_t lane, uint32_t n, const uint32_t *h_gid, const agc_hip_packed *pk, const uint64_t *h_off,
@@ -2284,11 +2370,10 @@ int agc_hip_lz_encode_begin_dev(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gi
     const int e = lz_encode_begin_enter(c, 1, n);
     if (e)
         return e > 0 ? AGC_HIP_OK : e;
-    agc_hip_ctx::Lane2 &L = c->lane(1);
-    PackedSrc src;
-    std::vector<uint64_t> off2;
-    CHK(pack_range(c, d_base, n, h_off, h_len, L.pk, L.s, src, off2)); // (the lane's own packed copy: it lives until end)
-    return lz_encode_begin_impl(c, 1, n, h_gid, src, off2.data(), h_len, h_rc);
+    agc_hip_ctx::Lane2 &L = c->lane(1); // (the lane's own packed copy: it lives until end)
+    return with_packed_bytes(c, d_base, n, h_off, h_len, L.pk, L.s, [&](const PackedSrc &src, const uint64_t *off2) {
+        return lz_encode_begin_impl(c, 1, n, h_gid, src, off2, h_len, h_rc);
+    });
 }
 
 int agc_hip_lz_encode_pending(agc_hip_ctx *c, uint32_t *h_n) { return agc_hip_lz_encode_pending_on(c, 0, h_n); }
@@ -2381,46 +2466,8 @@ int agc_hip_lz_encode_end_on(agc_hip_ctx *c, uint32_t lane, uint8_t *h_enc, uint
         (void)hipMemcpyToSymbol(HIP_SYMBOL(agc::g_phase_cnt), z, sizeof z);
     }
 #endif
-    static const bool laps = getenv("AGC_HIP_LAPS") != nullptr;
-    auto tnow = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double lt = laps ? tnow() : 0;
-    auto LAP = [&](const char *what) {
-        if (laps && n > 10000) {
-            const double t = tnow();
-            fprintf(stderr, "    lz_encode_end lap %s %.3f ms\n", what, t - lt);
-            lt = t;
-        }
-    };
-    for (uint32_t i = 0; i < n; ++i)
-        h_enc_off[i + 1] = h_enc_off[i] + L.h_lens[i];
-    const uint64_t tot = h_enc_off[n];
-    if (tot > enc_cap)
-        return AGC_HIP_ECAP; // (still in flight: call again with a larger buffer)
-    LAP("offsets");
-    if (tot) {
-        if (!h_enc)
-            return AGC_HIP_EINVAL;
-        CHK(ensure(c, L.d_dstoff, (size_t)n * 8, L.s));
-        CHK(upload(c, L.d_dstoff.p, h_enc_off, (size_t)n * 8, L.s));
-        // a pinned result buffer (agc_hip_host_alloc) is written by the gather itself, over the link: no second buffer, no copy
-        // engine; anything else gets the deltas compacted in HBM and copied
-        void *d_host = nullptr;
-        if (hipHostGetDevicePointer(&d_host, h_enc, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            d_host = nullptr;
-        }
-        if (!d_host)
-            CHK(ensure(c, L.d_compact, tot, L.s));
-        hipLaunchKernelGGL(gather_bytes_kernel, dim3(grid_for(n, 1, 8192)), dim3(256), 0, L.s, (const uint8_t *)L.d_scratch.p,
-                           (const SegDesc *)L.d_segs.p, (const uint32_t *)L.d_resv.p, (const uint64_t *)L.d_dstoff.p, n,
-                           d_host ? (uint8_t *)d_host : (uint8_t *)L.d_compact.p);
-        HIPCHK(c, hipGetLastError());
-        if (!d_host)
-            HIPCHK(c, hipMemcpyAsync(h_enc, L.d_compact.p, tot, hipMemcpyDeviceToHost, L.s));
-        LAP("queued");
-        HIPCHK(c, hipStreamSynchronize(L.s));
-        LAP("deltas on the host");
-    }
+    // (AGC_HIP_ECAP: still in flight -- call again with a larger buffer)
+    CHK(collect_deltas(c, {L.d_scratch, L.d_segs, L.d_resv, L.d_dstoff, L.d_compact}, L.s, n, L.h_lens, true, h_enc, enc_cap, h_enc_off, Laps("lz_encode_end", n)));
     L.pending = false;
     return AGC_HIP_OK;
 }
@@ -2554,20 +2601,9 @@ static int fetch_slices_impl(agc_hip_ctx *c, uint32_t n, const PackedSrc &src, c
         return AGC_HIP_OK;
     if (!h_out)
         return AGC_HIP_EINVAL;
-    if (!slices_inside(src, n, h_off, h_len))
-        return AGC_HIP_EINVAL;
-    CHK(ensure(c, c->d_compact, tot + 64));
-    std::vector<ViewJob> sl(n);
-    for (uint32_t i = 0; i < n; ++i)
-        sl[i] = {{src.words, src.esc_index, src.esc_bytes, h_off[i], h_len[i], h_rc ? (uint32_t)(h_rc[i] != 0) : 0u}, (uint8_t *)c->d_compact.p + h_out_off[i]};
-    CHK(ensure(c, c->d_slices, (size_t)n * sizeof(ViewJob)));
-    CHK(upload(c, c->d_slices.p, sl.data(), (size_t)n * sizeof(ViewJob), c->stream));
-    {
-        KTimer t(c, AGC_HIP_K_REVCOMP);
-        hipLaunchKernelGGL(slice_expand_kernel, dim3(grid_for(n, 1, 65536)), dim3(256), 0, c->stream, (const ViewJob *)c->d_slices.p, n);
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(h_out, c->d_compact.p, tot, hipMemcpyDeviceToHost, c->stream));
+    const SliceBufs B = slice_bufs(c);
+    CHK(put_view_jobs(c, B, c->stream, n, src, h_off, h_len, h_rc, h_out_off));
+    CHK(queue_expand(c, B, c->stream, n, h_out, tot, AGC_HIP_K_REVCOMP));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return AGC_HIP_OK;
 }
@@ -2575,24 +2611,9 @@ static int fetch_slices_impl(agc_hip_ctx *c, uint32_t n, const PackedSrc &src, c
 static int ref_lag_counts_impl(agc_hip_ctx *c, uint32_t n, const PackedSrc &src, const uint64_t *h_off, const uint32_t *h_len, const uint8_t *h_rc,
                                uint32_t *h_cnt, uint32_t *h_cur)
 {
-    if (!slices_inside(src, n, h_off, h_len))
-        return AGC_HIP_EINVAL;
-    std::vector<ViewJob> sl(n);
-    for (uint32_t i = 0; i < n; ++i)
-        sl[i] = {{src.words, src.esc_index, src.esc_bytes, h_off[i], h_len[i], h_rc ? (uint32_t)(h_rc[i] != 0) : 0u}, nullptr};
-    CHK(ensure(c, c->d_slices, (size_t)n * sizeof(ViewJob)));
-    CHK(ensure(c, c->d_lag, (size_t)n * 28 * 4 * 2));
-    CHK(upload(c, c->d_slices.p, sl.data(), (size_t)n * sizeof(ViewJob), c->stream));
-    uint32_t *d_cnt = (uint32_t *)c->d_lag.p, *d_cur = d_cnt + (size_t)n * 28;
-    const uint32_t split = n >= 2048 ? 1u : std::min<uint32_t>(32u, 2048u / n);
-    HIPCHK(c, hipMemsetAsync(c->d_lag.p, 0, (size_t)n * 28 * 4 * 2, c->stream));
-    {
-        KTimer t(c, AGC_HIP_K_REFSTORE);
-        hipLaunchKernelGGL(lag_counts_kernel, dim3(n * split), dim3(256), 0, c->stream, (const ViewJob *)c->d_slices.p, d_cnt, d_cur, split);
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(h_cnt, d_cnt, (size_t)n * 28 * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h_cur, d_cur, (size_t)n * 28 * 4, hipMemcpyDeviceToHost, c->stream));
+    const SliceBufs B = slice_bufs(c);
+    CHK(put_view_jobs(c, B, c->stream, n, src, h_off, h_len, h_rc, nullptr));
+    CHK(queue_lag_counts(c, B, c->stream, n, h_cnt, h_cur, AGC_HIP_K_REFSTORE));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return AGC_HIP_OK;
 }
@@ -2628,30 +2649,12 @@ int agc_hip_ref_store_begin_packed(agc_hip_ctx *c, uint32_t slot, uint32_t n_ref
         return AGC_HIP_OK;
     if (tot && !h_out)
         return AGC_HIP_EINVAL;
-    const PackedSrc src = src_of(pk);
-    if (!slices_inside(src, n, h_off, h_len))
-        return AGC_HIP_EINVAL;
-    CHK(ensure(c, R.d_out, tot + 64, st));
-    CHK(ensure(c, R.d_slices, (size_t)n * sizeof(ViewJob), st));
-    CHK(ensure(c, R.d_lag, std::max<size_t>(64, (size_t)n_refs * 28 * 4 * 2), st));
-    std::vector<ViewJob> sl(n);
-    for (uint32_t i = 0; i < n; ++i)
-        sl[i] = {{src.words, src.esc_index, src.esc_bytes, h_off[i], h_len[i], h_rc ? (uint32_t)(h_rc[i] != 0) : 0u}, (uint8_t *)R.d_out.p + h_out_off[i]};
-    CHK(upload(c, R.d_slices.p, sl.data(), (size_t)n * sizeof(ViewJob), st));
-    if (n_refs) {
-        uint32_t *d_cnt = (uint32_t *)R.d_lag.p, *d_cur = d_cnt + (size_t)n_refs * 28;
-        const uint32_t split = n_refs >= 2048 ? 1u : std::min<uint32_t>(32u, 2048u / n_refs);
-        HIPCHK(c, hipMemsetAsync(R.d_lag.p, 0, (size_t)n_refs * 28 * 4 * 2, st));
-        hipLaunchKernelGGL(lag_counts_kernel, dim3(n_refs * split), dim3(256), 0, st, (const ViewJob *)R.d_slices.p, d_cnt, d_cur, split);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(h_cnt, d_cnt, (size_t)n_refs * 28 * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(h_cur, d_cur, (size_t)n_refs * 28 * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (tot) {
-        hipLaunchKernelGGL(slice_expand_kernel, dim3(grid_for(n, 1, 65536)), dim3(256), 0, st, (const ViewJob *)R.d_slices.p, n);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(h_out, R.d_out.p, tot, hipMemcpyDeviceToHost, st));
-    }
+    const SliceBufs B = slice_bufs(R);
+    CHK(put_view_jobs(c, B, st, n, src_of(pk), h_off, h_len, h_rc, h_out_off));
+    if (n_refs)
+        CHK(queue_lag_counts(c, B, st, n_refs, h_cnt, h_cur, -1));
+    if (tot)
+        CHK(queue_expand(c, B, st, n, h_out, tot, -1));
     HIPCHK(c, hipEventRecord(R.done, st));
     R.pending = true;
     return AGC_HIP_OK;
@@ -2737,11 +2740,9 @@ int agc_hip_lz_estimate_batch_dev(agc_hip_ctx *c, uint32_t n, const uint32_t *h_
         return AGC_HIP_EINVAL;
     if (!n)
         return AGC_HIP_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    PackedSrc src;
-    std::vector<uint64_t> off2;
-    CHK(pack_range(c, d_base, n, h_off, h_len, c->pk1, c->stream, src, off2));
-    return lz_estimate_impl(c, n, h_gid, src, off2.data(), h_len, h_rc, h_cost, h_peak);
+    return with_packed_bytes(c, d_base, n, h_off, h_len, c->pk1, c->stream, [&](const PackedSrc &src, const uint64_t *off2) {
+        return lz_estimate_impl(c, n, h_gid, src, off2, h_len, h_rc, h_cost, h_peak);
+    });
 }
 
 int agc_hip_lz_cost_vector_batch_dev(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const uint8_t *d_base,
@@ -2752,11 +2753,9 @@ int agc_hip_lz_cost_vector_batch_dev(agc_hip_ctx *c, uint32_t n, const uint32_t 
         return AGC_HIP_EINVAL;
     if (!n)
         return AGC_HIP_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    PackedSrc src;
-    std::vector<uint64_t> off2;
-    CHK(pack_range(c, d_base, n, h_off, h_len, c->pk1, c->stream, src, off2));
-    return lz_cost_vector_impl(c, n, h_gid, src, off2.data(), h_len, h_rc, h_prefix_costs, h_costs);
+    return with_packed_bytes(c, d_base, n, h_off, h_len, c->pk1, c->stream, [&](const PackedSrc &src, const uint64_t *off2) {
+        return lz_cost_vector_impl(c, n, h_gid, src, off2, h_len, h_rc, h_prefix_costs, h_costs);
+    });
 }
 
 // host-resident texts --------------------------------------------------------
@@ -2765,10 +2764,9 @@ int agc_hip_lz_encode_batch(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, c
 {
     if (!c || (n && (!h_text || !h_off || !h_len)))
         return AGC_HIP_EINVAL;
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<uint64_t> doff;
-    CHK(stage_host_texts(c, n, h_text, h_off, h_len, doff));
-    return agc_hip_lz_encode_batch_dev(c, n, h_gid, (const uint8_t *)c->d_in.p, doff.data(), h_len, h_rc, h_enc, enc_cap, h_enc_off);
+    return with_host_texts(c, n, h_text, h_off, h_len, [&](const uint8_t *d_base, const uint64_t *doff) {
+        return agc_hip_lz_encode_batch_dev(c, n, h_gid, d_base, doff, h_len, h_rc, h_enc, enc_cap, h_enc_off);
+    });
 }
 
 int agc_hip_lz_estimate_batch(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const uint8_t *h_text, const uint64_t *h_off,
@@ -2776,10 +2774,9 @@ int agc_hip_lz_estimate_batch(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid,
 {
     if (!c || (n && (!h_text || !h_off || !h_len)))
         return AGC_HIP_EINVAL;
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<uint64_t> doff;
-    CHK(stage_host_texts(c, n, h_text, h_off, h_len, doff));
-    return agc_hip_lz_estimate_batch_dev(c, n, h_gid, (const uint8_t *)c->d_in.p, doff.data(), h_len, h_rc, h_cost, h_peak);
+    return with_host_texts(c, n, h_text, h_off, h_len, [&](const uint8_t *d_base, const uint64_t *doff) {
+        return agc_hip_lz_estimate_batch_dev(c, n, h_gid, d_base, doff, h_len, h_rc, h_cost, h_peak);
+    });
 }
 
 int agc_hip_lz_cost_vector_batch(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const uint8_t *h_text, const uint64_t *h_off,
@@ -2787,11 +2784,9 @@ int agc_hip_lz_cost_vector_batch(agc_hip_ctx *c, uint32_t n, const uint32_t *h_g
 {
     if (!c || (n && (!h_text || !h_off || !h_len)))
         return AGC_HIP_EINVAL;
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<uint64_t> doff;
-    CHK(stage_host_texts(c, n, h_text, h_off, h_len, doff));
-    return agc_hip_lz_cost_vector_batch_dev(c, n, h_gid, (const uint8_t *)c->d_in.p, doff.data(), h_len, h_rc, h_prefix_costs,
-                                            h_costs);
+    return with_host_texts(c, n, h_text, h_off, h_len, [&](const uint8_t *d_base, const uint64_t *doff) {
+        return agc_hip_lz_cost_vector_batch_dev(c, n, h_gid, d_base, doff, h_len, h_rc, h_prefix_costs, h_costs);
+    });
 }
 
 int agc_hip_lz_split_point_batch_dev(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid1, const uint32_t *h_gid2,
@@ -2803,11 +2798,9 @@ int agc_hip_lz_split_point_batch_dev(agc_hip_ctx *c, uint32_t n, const uint32_t 
         return AGC_HIP_EINVAL;
     if (!n)
         return AGC_HIP_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    PackedSrc src;
-    std::vector<uint64_t> off2;
-    CHK(pack_range(c, d_base, n, h_off, h_len, c->pk1, c->stream, src, off2));
-    return lz_split_point_impl(c, n, h_gid1, h_gid2, src, off2.data(), h_len, h_rc1, h_prefix1, h_rc2, h_prefix2, h_best_pos, h_best_sum);
+    return with_packed_bytes(c, d_base, n, h_off, h_len, c->pk1, c->stream, [&](const PackedSrc &src, const uint64_t *off2) {
+        return lz_split_point_impl(c, n, h_gid1, h_gid2, src, off2, h_len, h_rc1, h_prefix1, h_rc2, h_prefix2, h_best_pos, h_best_sum);
+    });
 }
 
 int agc_hip_fetch_slices_dev(agc_hip_ctx *c, uint32_t n, const uint8_t *d_base, const uint64_t *h_off, const uint32_t *h_len,
@@ -2818,16 +2811,11 @@ int agc_hip_fetch_slices_dev(agc_hip_ctx *c, uint32_t n, const uint8_t *d_base, 
     h_out_off[0] = 0;
     if (!n)
         return AGC_HIP_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    PackedSrc src;
-    std::vector<uint64_t> off2;
-    CHK(pack_range(c, d_base, n, h_off, h_len, c->pk1, c->stream, src, off2));
-    return fetch_slices_impl(c, n, src, off2.data(), h_len, h_rc, h_out, out_cap, h_out_off);
+    return with_packed_bytes(c, d_base, n, h_off, h_len, c->pk1, c->stream, [&](const PackedSrc &src, const uint64_t *off2) {
+        return fetch_slices_impl(c, n, src, off2, h_len, h_rc, h_out, out_cap, h_out_off);
+    });
 }
 
-// ---------------------------------------------------------------------------
-// a13 helper
-// ---------------------------------------------------------------------------
 int agc_hip_ref_lag_counts_dev(agc_hip_ctx *c, uint32_t n, const uint8_t *d_base, const uint64_t *h_off, const uint32_t *h_len,
                                const uint8_t *h_rc, uint32_t *h_cnt, uint32_t *h_cur)
 {
@@ -2835,11 +2823,9 @@ int agc_hip_ref_lag_counts_dev(agc_hip_ctx *c, uint32_t n, const uint8_t *d_base
         return AGC_HIP_EINVAL;
     if (!n)
         return AGC_HIP_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    PackedSrc src;
-    std::vector<uint64_t> off2;
-    CHK(pack_range(c, d_base, n, h_off, h_len, c->pk1, c->stream, src, off2));
-    return ref_lag_counts_impl(c, n, src, off2.data(), h_len, h_rc, h_cnt, h_cur);
+    return with_packed_bytes(c, d_base, n, h_off, h_len, c->pk1, c->stream, [&](const PackedSrc &src, const uint64_t *off2) {
+        return ref_lag_counts_impl(c, n, src, off2, h_len, h_rc, h_cnt, h_cur);
+    });
 }
 
 // ---------------------------------------------------------------------------

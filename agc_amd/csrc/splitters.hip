@@ -149,8 +149,8 @@ extern "C" int agc_hip_determine_splitters_dev(agc_hip_ctx *c, const uint8_t *d_
         return fail(AGC_HIP_ENODEV);
     if ((rc = ensure(c, c->d_ranges, ranges.size() * sizeof(ScanRange))))
         return fail(rc);
-    if (hipMemcpyAsync(c->d_ranges.p, ranges.data(), ranges.size() * sizeof(ScanRange), hipMemcpyHostToDevice, c->stream) != hipSuccess)
-        return fail(AGC_HIP_ENODEV);
+    if ((rc = upload(c, c->d_ranges.p, ranges.data(), ranges.size() * sizeof(ScanRange), c->stream)))
+        return fail(rc);
     {
         KTimer t(c, AGC_HIP_K_SCAN);
         hipLaunchKernelGGL(kmer_enum_kernel, dim3(grid_for((uint32_t)ranges.size(), 4, 4096)), dim3(256), 0, c->stream, d_codes,
@@ -263,15 +263,15 @@ extern "C" int agc_hip_determine_splitters_dev(agc_hip_ctx *c, const uint8_t *d_
                 (void)hipFree(dpos.p);
             return fail(rc);
         }
-        (void)hipMemcpyAsync(dpos.p, spl_pos.data(), spl_pos.size() * 8, hipMemcpyHostToDevice, c->stream);
+        rc = upload(c, dpos.p, spl_pos.data(), spl_pos.size() * 8, c->stream);
         hipLaunchKernelGGL(kmers_at_kernel, dim3((uint32_t)((spl_pos.size() + 255) / 256)), dim3(256), 0, c->stream, d_codes,
                            (const uint64_t *)dpos.p, (uint32_t)spl_pos.size(), k, (uint64_t *)dout.p);
         (void)hipMemcpyAsync(spl.data(), dout.p, spl.size() * 8, hipMemcpyDeviceToHost, c->stream);
         const hipError_t e2 = hipStreamSynchronize(c->stream);
         (void)hipFree(dpos.p);
         (void)hipFree(dout.p);
-        if (e2 != hipSuccess)
-            return fail(AGC_HIP_ENODEV);
+        if (rc || e2 != hipSuccess)
+            return fail(rc ? rc : AGC_HIP_ENODEV);
     }
     release();
     std::sort(spl.begin(), spl.end());

@@ -328,6 +328,86 @@ def test_packed_references_out_of_a_sample(hip_ctx, oracle):
         assert np.array_equal(enc[int(eoff[i]):int(eoff[i + 1])], oracle.LZ(stored, mml).encode(texts[i])), i
 
 
+@pytest.mark.parametrize("gap_fill", ["acgt", "n"])
+def test_many_short_slices(hip_ctx, oracle, gap_fill):
+    """5000 sequences of one packed sample through every entry point that uploads a descriptor per sequence (ViewJob 40 B, SegDesc
+    64 B: 200 KB and 320 KB, more than a piece of the smallest upload ring): slices, lag counts, encodes in one call and on both
+    lanes, and both slots of the reference store"""
+    rng = np.random.default_rng(909)
+    mml, n, gid0 = 20, 5000, 11000 if gap_fill == "acgt" else 11100
+    long_at = np.sort(rng.choice(n, 12, replace=False))
+    refs = [synth.random_seq(rng, int(m)) for m in rng.integers(300, 2001, 6)]
+    group = rng.integers(0, 6, n)
+    texts = []
+    for i in range(n):
+        r = refs[group[i]]
+        m = int(rng.integers(1, 49))
+        a = int(rng.integers(0, r.size - m))
+        texts.append(r[a:a + m].copy())
+    for j, i in enumerate(long_at):  # the first six long texts are the references themselves, the others mutated copies
+        group[i] = j % 6
+        texts[i] = refs[j].copy() if j < 6 else synth.mutate(rng, refs[j % 6], 0.01, indels=1)
+    pk, keep, off, ln, buf = _packed_sample(hip_ctx, texts, rng, gap_fill)
+    gids = (gid0 + group).astype(np.uint32)
+    hip_ctx.ref_register_batch_packed(gid0 + np.arange(6), pk, off[long_at[:6]], ln[long_at[:6]], np.zeros(6, np.uint8), mml)
+    checked = sorted(set(range(0, n, 97)) | set(int(i) for i in long_at))
+    rc = (np.arange(n) % 2).astype(np.uint8)
+
+    def want_slice(i, r):
+        t = buf[int(off[i]):int(off[i]) + int(ln[i])]
+        return oracle.rev_comp(t) if r else t
+
+    back, boff = hip_ctx.fetch_slices_packed(pk, off, ln, rc=rc)
+    assert np.array_equal(boff, np.concatenate([[0], np.cumsum(ln.astype(np.uint64))]))
+    for i in range(n):
+        assert np.array_equal(back[int(boff[i]):int(boff[i + 1])], want_slice(i, rc[i])), i
+    cnt, cur = hip_ctx.ref_lag_counts_packed(pk, off, ln)
+    for i in checked:
+        wc, wu = oracle.ref_lag_counts(texts[i])
+        assert np.array_equal(cnt[i], wc) and np.array_equal(cur[i], wu), i
+    # two encodes in flight, one per lane, collected in the other order; lane 1 with every other text, reverse-complemented
+    half = np.arange(0, n, 2)
+    ones = np.ones(half.size, np.uint8)
+    hip_ctx.lz_encode_begin_packed(pk, gids, off, ln, lane=0)
+    hip_ctx.lz_encode_begin_packed(pk, gids[half], off[half], ln[half], rc=ones, lane=1)
+    enc_b, eoff_b = hip_ctx.lz_encode_end_on(1)
+    enc_a, eoff_a = hip_ctx.lz_encode_end_on(0)
+    one, ooff = hip_ctx.lz_encode_batch_packed(pk, gids, off, ln)
+    assert np.array_equal(enc_a, one) and np.array_equal(eoff_a, ooff)
+    one_b, ooff_b = hip_ctx.lz_encode_batch_packed(pk, gids[half], off[half], ln[half], rc=ones)
+    assert np.array_equal(enc_b, one_b) and np.array_equal(eoff_b, ooff_b)
+    lz = [oracle.LZ(r, mml) for r in refs]
+    for i in checked:
+        assert np.array_equal(one[int(ooff[i]):int(ooff[i + 1])], lz[group[i]].encode(texts[i])), i
+        if i % 2 == 0:
+            j = i // 2
+            assert np.array_equal(one_b[int(ooff_b[j]):int(ooff_b[j + 1])], lz[group[i]].encode(oracle.rev_comp(texts[i]))), i
+    # both slots of the reference store begun before either is collected
+    other = np.arange(2, n, 5)
+    hip_ctx.ref_store_begin_packed(0, 40, pk, off, ln, rc)
+    hip_ctx.ref_store_begin_packed(1, 40, pk, off[other], ln[other], rc[other])
+    for slot, sel in ((1, other), (0, np.arange(n))):
+        scnt, scur, sout, sooff = hip_ctx.ref_store_end(slot)
+        wout, wooff = hip_ctx.fetch_slices_packed(pk, off[sel], ln[sel], rc=rc[sel])
+        wcnt, wcur = hip_ctx.ref_lag_counts_packed(pk, off[sel[:40]], ln[sel[:40]], rc=rc[sel[:40]])
+        assert np.array_equal(sout, wout) and np.array_equal(sooff, wooff), slot
+        assert np.array_equal(scnt, wcnt) and np.array_equal(scur, wcur), slot
+
+
+def test_lz_uploads_through_a_ring_of_1_MB():
+    """AGC_HIP_UPLOAD_RING_MB=1: a piece of the upload ring is 128 KB, so the descriptor arrays of test_many_short_slices and --
+    with AGC_HIP_LZ_CHUNK=64 -- the chunk list of the long texts (some 30 000 ChunkJobs of 8 B) each go over in several pieces.
+    The ring's size is read once per process: a child process"""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, AGC_HIP_UPLOAD_RING_MB="1", AGC_HIP_LZ_CHUNK="64")
+    sel = ["tests/test_gpu_lz.py", "-k", "many_short_slices or chunked_parse_of_few_long_texts"]
+    r = subprocess.run([sys.executable, "-m", "pytest", "-m", "gpu", "-x", "-q"] + sel, capture_output=True, text=True, timeout=600, env=env, cwd=root)
+    assert r.returncode == 0, r.stdout[-3000:]
+
+
 # ---- the parse in chunks (lz_kernels.hip: ChunkCtl; launch_parse picks it for launches of few, long texts) --------------------------
 def _long_cases(oracle):
     """few, long, diverged texts -- the launches the chunked parse is made for: 2.5 % substitutions with indels, a text whose second
@@ -397,8 +477,8 @@ def test_lz_suite_with_every_launch_parsed_in_chunks(chunk):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, AGC_HIP_LZ_CHUNK=str(chunk))
-    sel = ["tests/test_gpu_lz.py", "-k", "not every_launch_parsed_in_chunks"]
+    sel = ["tests/test_gpu_lz.py", "-k", "not every_launch_parsed_in_chunks and not ring_of_1_MB"]
     if chunk == 300:
-        sel = ["tests/test_gpu_lz.py", "tests/test_gpu_archive.py", "-k", "not every_launch_parsed_in_chunks and not full_size"]
+        sel = ["tests/test_gpu_lz.py", "tests/test_gpu_archive.py", "-k", "not every_launch_parsed_in_chunks and not ring_of_1_MB and not full_size"]
     r = subprocess.run([sys.executable, "-m", "pytest", "-m", "gpu", "-x", "-q"] + sel, capture_output=True, text=True, timeout=1500, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-3000:]
