@@ -14,7 +14,8 @@ LIB_PATH = os.path.join(HERE, "libagc_hip.so")
 
 OK, ENODEV, EINVAL, ENOMEM, ECAP, ENOREF = 0, -1, -2, -3, -4, -5
 K_SCAN, K_INDEX, K_ENCODE, K_ESTIMATE, K_COSTVEC, K_REVCOMP, K_PREPROCESS, K_REFSTORE = range(8)
-K_NAMES = ["scan", "index", "encode", "estimate", "costvec", "revcomp", "preprocess", "refstore", "zstd", "filter", "segments", "pack"]
+K_NAMES = ["scan", "index", "encode", "estimate", "costvec", "revcomp", "preprocess", "refstore", "zstd", "filter", "segments", "pack",
+           "decode_scan", "decode_write"]
 
 # every symbol include/agc_hip.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
@@ -28,6 +29,7 @@ SYMBOLS = [
     "agc_hip_ref_register", "agc_hip_ref_register_batch_dev", "agc_hip_ref_get", "agc_hip_ref_index_get",
     "agc_hip_lz_encode_batch_dev", "agc_hip_lz_encode_batch", "agc_hip_lz_encode_begin_dev", "agc_hip_lz_encode_end", "agc_hip_lz_encode_pending",
     "agc_hip_lz_encode_begin_packed_on", "agc_hip_lz_encode_end_on", "agc_hip_lz_encode_pending_on", "agc_hip_lz_encode_drop_on",
+    "agc_hip_lz_decode_batch", "agc_hip_lz_decode_batch_dev",
     "agc_hip_host_alloc", "agc_hip_host_free",
     "agc_hip_lz_estimate_batch_dev", "agc_hip_lz_estimate_batch",
     "agc_hip_lz_cost_vector_batch_dev", "agc_hip_lz_cost_vector_batch",
@@ -125,6 +127,8 @@ def load():
     L.agc_hip_lz_encode_begin_dev.argtypes = [vp, C.c_uint32, u32p, vp, u64p, u32p, u8p]
     L.agc_hip_lz_encode_end.argtypes = [vp, u8p, C.c_uint64, u64p]
     L.agc_hip_lz_encode_pending.argtypes = [vp, u32p]
+    L.agc_hip_lz_decode_batch.argtypes = [vp, C.c_uint32, u32p, u8p, u64p, u8p, u8p, C.c_uint64, u64p]
+    L.agc_hip_lz_decode_batch_dev.argtypes = [vp, C.c_uint32, u32p, u8p, u64p, u8p, vp, C.c_uint64, u64p]
     L.agc_hip_host_alloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
     L.agc_hip_host_free.argtypes = [vp, vp]
     L.agc_hip_lz_estimate_batch_dev.argtypes = [vp, C.c_uint32, u32p, vp, u64p, u32p, u8p, u32p, u32p]
@@ -594,6 +598,32 @@ class Context:
         self._chk(rc_)
         self._enc_pending = None
         return enc[:int(eoff[-1])], eoff
+
+    def _decode_args(self, enc, enc_off, gids, rc):
+        e, eo, g = _a(enc, np.uint8), _a(enc_off, np.uint64), _a(gids, np.uint32)
+        r = _a(rc, np.uint8) if rc is not None else None
+        assert eo.size == g.size + 1 and (r is None or r.size == g.size) and (g.size == 0 or int(eo[-1]) <= e.size)
+        return e, eo, g, r
+
+    def lz_decode_batch(self, enc, enc_off, gids, rc=None, out_cap=None):
+        """deltas enc[enc_off[s]:enc_off[s+1]] against the references of gids -> (symbols, out_off[n+1]); rc[s]: reverse-complemented"""
+        e, eo, g, r = self._decode_args(enc, enc_off, gids, rc)
+        ooff = np.zeros(g.size + 1, np.uint64)
+        if out_cap is None:  # (the first call sizes the output: AGC_HIP_ECAP leaves the size needed in out_off[n])
+            rc_ = self.L.agc_hip_lz_decode_batch(self.h, g.size, _p(g, u32p), _p(e, u8p), _p(eo, u64p), _p(r, u8p), None, 0, _p(ooff, u64p))
+            if rc_ != ECAP:
+                self._chk(rc_)
+            out_cap = int(ooff[-1])
+        out = np.empty(out_cap, np.uint8)
+        self._chk(self.L.agc_hip_lz_decode_batch(self.h, g.size, _p(g, u32p), _p(e, u8p), _p(eo, u64p), _p(r, u8p), _p(out, u8p), out_cap, _p(ooff, u64p)))
+        return out[:int(ooff[-1])], ooff
+
+    def lz_decode_batch_dev(self, enc, enc_off, gids, d_out, out_cap, rc=None):
+        """the same, the symbols left at the device address d_out (out_cap bytes) -> out_off[n+1]"""
+        e, eo, g, r = self._decode_args(enc, enc_off, gids, rc)
+        ooff = np.zeros(g.size + 1, np.uint64)
+        self._chk(self.L.agc_hip_lz_decode_batch_dev(self.h, g.size, _p(g, u32p), _p(e, u8p), _p(eo, u64p), _p(r, u8p), d_out, out_cap, _p(ooff, u64p)))
+        return ooff
 
     def lz_encode_batch(self, text, gids, off, length, rc=None, enc_cap=None):
         text = _a(text, np.uint8)

@@ -20,6 +20,7 @@
 #include "pack_kernels.hip"
 #include "lz_kernels.hip"
 #include "seg_kernels.hip"
+#include "lz_decode_kernels.hip"
 #include "zstd_kernels.hip"
 
 using namespace agc;
@@ -113,6 +114,7 @@ struct agc_hip_ctx {
     } seg_state;
     DevBuf d_ranges, d_hits, d_counter, d_segs, d_slices, d_scratch, d_resv, d_resp, d_dstoff, d_compact,
         d_jobs, d_counts, d_in, d_pp_cnt, d_pp_off, d_pp_total, d_lag, d_sample, d_zsrc, d_zdst, d_zws, d_zjobs, d_zsize, d_zout, d_zdstoff, d_maybe, d_fjobs;
+    DevBuf d_dec_enc, d_dec_jobs, d_dec_res, d_dec_out; // agc_hip_lz_decode_batch*: the deltas, their descriptors, lengths + status, the symbols
 
     PackTemp pk1;        // byte-input entry points on the first stream
     PackTemp pk_sample;  // agc_hip_sample_pack
@@ -749,7 +751,7 @@ void agc_hip_destroy(agc_hip_ctx *c)
     DevBuf *bufs[] = {&c->d_table, &c->d_bloom, &c->d_bloom2, &c->d_sbloom, &c->d_refs, &c->d_ranges, &c->d_hits, &c->d_counter, &c->d_segs, &c->d_slices,
                       &c->d_scratch, &c->d_resv, &c->d_resp, &c->d_dstoff, &c->d_compact, &c->d_jobs, &c->d_counts,
                       &c->d_in, &c->d_pp_cnt, &c->d_pp_off, &c->d_pp_total, &c->d_lag, &c->d_sample, &c->d_zsrc, &c->d_zdst, &c->d_zws,
-                      &c->d_zjobs, &c->d_zsize, &c->d_zout, &c->d_zdstoff, &c->d_maybe, &c->d_fjobs,
+                      &c->d_zjobs, &c->d_zsize, &c->d_zout, &c->d_zdstoff, &c->d_maybe, &c->d_fjobs, &c->d_dec_enc, &c->d_dec_jobs, &c->d_dec_res, &c->d_dec_out,
                       &c->l2.d_segs, &c->l2.d_counter, &c->l2.d_resv, &c->l2.d_resp, &c->l2.d_scratch, &c->l2.d_dstoff,
                       &c->l2.d_compact, &c->l3.d_segs, &c->l3.d_counter, &c->l3.d_resv, &c->l3.d_resp, &c->l3.d_scratch, &c->l3.d_dstoff,
                       &c->l3.d_compact, &c->l2.d_n, &c->l3.d_n, &c->d_esc_jobs, &c->d_flags, &c->d_gmap, &c->d_gmap_stage, &c->d_segwork, &c->d_segtmp};
@@ -2318,6 +2320,82 @@ static int lz_encode_begin_enter(agc_hip_ctx *c, int lane, uint32_t n)
     return AGC_HIP_OK;
 }
 
+// The decode (include/agc_hip.h) on the first stream: lz_decode_scan_kernel gives every delta's length and status, the host lays
+// the output out, lz_decode_write_kernel fills it -- launched only when every delta of the batch is well formed.
+// d_out: the caller's device buffer, or nullptr: the context's, copied to h_out.
+static int lz_decode_impl(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const uint8_t *h_enc, const uint64_t *h_enc_off, const uint8_t *h_rc,
+                          uint8_t *h_out, uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_off)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        if (h_gid[i] >= c->refs.size() || !c->refs[h_gid[i]].valid) {
+            c->err = "lz_decode: delta " + std::to_string(i) + ": group " + std::to_string(h_gid[i]) + " has no registered reference";
+            return AGC_HIP_EINVAL;
+        }
+        if (h_enc_off[i + 1] < h_enc_off[i]) {
+            c->err = "lz_decode: delta " + std::to_string(i) + " ends in front of its start";
+            return AGC_HIP_EINVAL;
+        }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(upload_refs(c));
+    const uint64_t e0 = h_enc_off[0], enc_bytes = h_enc_off[n] - e0;
+    std::vector<DecodeJob> jobs(n);
+    for (uint32_t i = 0; i < n; ++i)
+        jobs[i] = {h_enc_off[i] - e0, h_enc_off[i + 1] - h_enc_off[i], 0, 0, h_gid[i], h_rc && h_rc[i] ? 1u : 0u, 0};
+    CHK(ensure(c, c->d_dec_enc, enc_bytes + 64));
+    CHK(ensure(c, c->d_dec_jobs, (size_t)n * sizeof(DecodeJob)));
+    CHK(ensure(c, c->d_dec_res, (size_t)n * sizeof(DecodeResult)));
+    if (enc_bytes)
+        CHK(upload(c, c->d_dec_enc.p, h_enc + e0, enc_bytes, c->stream));
+    CHK(upload(c, c->d_dec_jobs.p, jobs.data(), (size_t)n * sizeof(DecodeJob), c->stream));
+    const dim3 grid((n + 3) / 4), block(4 * WAVE); // a wave per delta
+    {
+        KTimer t(c, AGC_HIP_K_DECODE_SCAN);
+        hipLaunchKernelGGL(lz_decode_scan_kernel, grid, block, 0, c->stream, (const RefDesc *)c->d_refs.p, (const DecodeJob *)c->d_dec_jobs.p, n,
+                           (const uint8_t *)c->d_dec_enc.p, (DecodeResult *)c->d_dec_res.p);
+    }
+    HIPCHK(c, hipGetLastError());
+    std::vector<DecodeResult> res(n);
+    HIPCHK(c, hipMemcpyAsync(res.data(), c->d_dec_res.p, (size_t)n * sizeof(DecodeResult), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < n; ++i)
+        if (res[i].status != lzd::OK) {
+            static const char *why[] = {"", "a truncated or malformed token", "'!' at or past the end of the reference", "a match outside the reference",
+                                        "more than 2^32 - 1 decoded symbols"};
+            c->err = "lz_decode: delta " + std::to_string(i) + " is rejected: " + why[res[i].status <= lzd::TOO_LONG ? res[i].status : 1];
+            return AGC_HIP_EINVAL;
+        }
+    uint64_t tot = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        h_out_off[i] = tot;
+        jobs[i].out_off = tot;
+        jobs[i].out_len = res[i].len;
+        tot += res[i].len;
+    }
+    h_out_off[n] = tot;
+    if (tot > out_cap) {
+        c->err = "lz_decode: the output buffer holds " + std::to_string(out_cap) + " bytes, " + std::to_string(tot) + " are needed";
+        return AGC_HIP_ECAP;
+    }
+    if (!tot)
+        return AGC_HIP_OK;
+    if (!d_out) {
+        CHK(ensure(c, c->d_dec_out, tot + 64));
+        d_out = (uint8_t *)c->d_dec_out.p;
+    }
+    CHK(upload(c, c->d_dec_jobs.p, jobs.data(), (size_t)n * sizeof(DecodeJob), c->stream)); // (now with where each delta's symbols go)
+    {
+        KTimer t(c, AGC_HIP_K_DECODE_WRITE);
+        hipLaunchKernelGGL(lz_decode_write_kernel, grid, block, 0, c->stream, (const RefDesc *)c->d_refs.p, (const DecodeJob *)c->d_dec_jobs.p, n,
+                           (const uint8_t *)c->d_dec_enc.p, d_out);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (h_out)
+        HIPCHK(c, hipMemcpyAsync(h_out, d_out, tot, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return AGC_HIP_OK;
+}
+
 extern "C" {
 
 int agc_hip_lz_encode_batch_packed(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const agc_hip_packed *pk, const uint64_t *h_off,
@@ -2470,6 +2548,28 @@ int agc_hip_lz_encode_end_on(agc_hip_ctx *c, uint32_t lane, uint8_t *h_enc, uint
     CHK(collect_deltas(c, {L.d_scratch, L.d_segs, L.d_resv, L.d_dstoff, L.d_compact}, L.s, n, L.h_lens, true, h_enc, enc_cap, h_enc_off, Laps("lz_encode_end", n)));
     L.pending = false;
     return AGC_HIP_OK;
+}
+
+int agc_hip_lz_decode_batch(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const uint8_t *h_enc, const uint64_t *h_enc_off, const uint8_t *h_rc,
+                            uint8_t *h_out, uint64_t out_cap, uint64_t *h_out_off)
+{
+    if (!c || !h_out_off || (n && (!h_gid || !h_enc_off || (h_enc_off[n] > h_enc_off[0] && !h_enc))) || (out_cap && !h_out))
+        return AGC_HIP_EINVAL;
+    h_out_off[0] = 0;
+    if (!n)
+        return AGC_HIP_OK;
+    return lz_decode_impl(c, n, h_gid, h_enc, h_enc_off, h_rc, h_out, nullptr, out_cap, h_out_off);
+}
+
+int agc_hip_lz_decode_batch_dev(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const uint8_t *h_enc, const uint64_t *h_enc_off, const uint8_t *h_rc,
+                                uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_off)
+{
+    if (!c || !h_out_off || (n && (!h_gid || !h_enc_off || (h_enc_off[n] > h_enc_off[0] && !h_enc))) || (out_cap && !d_out))
+        return AGC_HIP_EINVAL;
+    h_out_off[0] = 0;
+    if (!n)
+        return AGC_HIP_OK;
+    return lz_decode_impl(c, n, h_gid, h_enc, h_enc_off, h_rc, nullptr, d_out, out_cap, h_out_off);
 }
 
 // pinned host memory for the buffers results are copied into (a copy into pageable memory goes through a bounce buffer)

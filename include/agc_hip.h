@@ -60,7 +60,9 @@ enum {
     AGC_HIP_K_FILTER = 9, /* key_filter_kernel: the "may match" bitmaps of the estimate / cost-vector parses */
     AGC_HIP_K_SEGMENTS = 10, /* agc_hip_segments_packed: hits -> segments -> group look-up -> encode descriptors (seg_kernels.hip) */
     AGC_HIP_K_PACK = 11,     /* agc_hip_pack_fasta_*: raw FASTA bodies -> the 2-bit packed sample in one pass (pack_kernels.hip) */
-    AGC_HIP_K_COUNT = 12
+    AGC_HIP_K_DECODE_SCAN = 12,  /* lz_decode_scan_kernel: length and status of every delta (lz_decode_kernels.hip) */
+    AGC_HIP_K_DECODE_WRITE = 13, /* lz_decode_write_kernel: the decoded symbols */
+    AGC_HIP_K_COUNT = 14
 };
 int agc_hip_timing_enable(agc_hip_ctx *ctx, int on);
 int agc_hip_timing_reset(agc_hip_ctx *ctx);
@@ -316,6 +318,19 @@ int agc_hip_lz_encode_pending_on(agc_hip_ctx *ctx, uint32_t lane, uint32_t *h_n)
 /* gives up the encode in flight on a lane (waits for its kernels, delivers nothing): a host that prepared a sample ahead of its
  * turn and has to prepare it again (adaptive mode in the N-rank mode: the splitter set grew meanwhile) */
 int agc_hip_lz_encode_drop_on(agc_hip_ctx *ctx, uint32_t lane);
+
+/* Replaces CLZDiff_V2::Decode (src/common/lz_diff.cpp:801-836) for a batch of deltas against registered groups.
+ * delta s = h_enc[h_enc_off[s] .. h_enc_off[s+1]); decoded s = out[h_out_off[s] .. h_out_off[s+1]), one symbol code per byte,
+ * reverse-complemented when h_rc && h_rc[s].  AGC_HIP_ECAP: out_cap too small, h_out_off[0..n] is filled and h_out_off[n] is the
+ * size needed, nothing is written to out.  AGC_HIP_EINVAL: unknown gid or a malformed delta (nothing is written to out; the error
+ * text names the first such delta).  A delta is malformed when a token is truncated, a number has more than 10 digits, a '!'
+ * literal or a match reaches outside the reference, or it decodes to 2^32 symbols or more.  Runs on the context's first stream:
+ * an encode in flight on a lane goes on beside it. */
+int agc_hip_lz_decode_batch(agc_hip_ctx *ctx, uint32_t n, const uint32_t *h_gid, const uint8_t *h_enc, const uint64_t *h_enc_off,
+                            const uint8_t *h_rc, uint8_t *h_out, uint64_t out_cap, uint64_t *h_out_off);
+/* the same, the decoded symbols left in device memory (d_out: out_cap bytes the caller owns) */
+int agc_hip_lz_decode_batch_dev(agc_hip_ctx *ctx, uint32_t n, const uint32_t *h_gid, const uint8_t *h_enc, const uint64_t *h_enc_off,
+                                const uint8_t *h_rc, uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_off);
 
 /* Pinned host memory for result buffers (device-to-host copies into pageable memory go through a bounce buffer at a
  * fraction of the link rate).  Freed by agc_hip_host_free or with the context. */
