@@ -245,6 +245,12 @@ class Context:
             out[n] = (ms.value, ln.value)
         return out
 
+    def host_alloc(self, nbytes):
+        """pinned host memory of the context's (agc_hip_host_alloc) -> its address; what nobody hands back goes with the context"""
+        p = vp()
+        self._chk(self.L.agc_hip_host_alloc(self.h, int(nbytes), C.byref(p)))
+        return p.value
+
     # ---- a1 -----------------------------------------------------------------
     def preprocess_dev(self, d_raw, n_raw, d_codes):
         n = C.c_uint64()

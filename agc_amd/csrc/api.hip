@@ -27,14 +27,54 @@ using namespace agc;
 
 namespace {
 
-struct DevBuf {
+// What the context holds, it holds through these: each frees its memory or destroys its handle when it goes, and can be moved but
+// not copied.  Nothing else in the library calls hipFree, hipHostFree, hipEventDestroy or hipStreamDestroy (agc_hip_host_free, which
+// hands a pinned buffer back early, goes through release() too).
+template <hipError_t (*Free)(void *)> struct OwnedMem {
     void *p = nullptr;
     size_t cap = 0;
+    OwnedMem() = default;
+    OwnedMem(void *p_, size_t cap_) : p(p_), cap(cap_) {}
+    OwnedMem(OwnedMem &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    OwnedMem &operator=(OwnedMem &&o) noexcept
+    {
+        if (this != &o) {
+            (void)release();
+            std::swap(p, o.p), std::swap(cap, o.cap);
+        }
+        return *this;
+    }
+    ~OwnedMem() { (void)release(); }
+    hipError_t release()
+    {
+        const hipError_t e = p ? Free(p) : hipSuccess;
+        p = nullptr, cap = 0;
+        return e;
+    }
+    template <class T> T *as() const { return (T *)p; }
 };
+using DevBuf = OwnedMem<hipFree>;        // device memory (grown by ensure)
+using PinnedBuf = OwnedMem<hipHostFree>; // pinned host memory (grown by ensure_pinned)
 
+template <class H, hipError_t (*Destroy)(H)> struct OwnedHandle {
+    H h = nullptr; // (made where it is first needed: hipStreamCreate* / hipEventCreate* write here)
+    OwnedHandle() = default;
+    OwnedHandle(OwnedHandle &&o) noexcept : h(o.h) { o.h = nullptr; }
+    OwnedHandle &operator=(OwnedHandle &&) = delete;
+    ~OwnedHandle()
+    {
+        if (h)
+            (void)Destroy(h);
+    }
+    operator H() const { return h; }
+};
+using Stream = OwnedHandle<hipStream_t, hipStreamDestroy>;
+using Event = OwnedHandle<hipEvent_t, hipEventDestroy>;
+
+// a chunk of the reference arena: mem.cap usable bytes (the allocation has a tail slack behind them), `used` of them handed out
 struct ArenaChunk {
-    uint8_t *p;
-    size_t size, used;
+    DevBuf mem;
+    size_t used = 0;
 };
 
 // a 2-bit packed buffer the LZ entry points read sequences from (sym_view.h): the caller's sample, or a temporary one
@@ -55,11 +95,11 @@ struct PackTemp {
 
 struct agc_hip_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t zstream = nullptr; // the entropy stage's own stream: agc_hip_zstd17_batch may run beside every other entry point
-    hipStream_t zstream2 = nullptr; // ... and a second one: the one-lane kernel (inputs > 16 KiB) runs BESIDE the group kernel
-    hipEvent_t zev_a = nullptr, zev_b = nullptr;
-    hipEvent_t zev_wait = nullptr; // (blocking-sync: the thread that waits for a launch of the entropy stage sleeps, its core is the host pool's)
+    Stream stream;  // the steps' stream
+    Stream zstream; // the entropy stage's own stream: agc_hip_zstd17_batch may run beside every other entry point
+    Stream zstream2; // ... and a second one: the one-lane kernel (inputs > 16 KiB) runs BESIDE the group kernel
+    Event zev_a, zev_b;
+    Event zev_wait; // (blocking-sync: the thread that waits for a launch of the entropy stage sleeps, its core is the host pool's)
     bool zstd_background = false;  // agc_hip_zstd17_background: launches leave the LDS to the kernels of the other streams
     std::string err;
 
@@ -80,10 +120,10 @@ struct agc_hip_ctx {
     // agc_hip_ref_store_begin_packed / _end: two slots, a stream and buffers of their own (the steps' stream never waits for them)
     struct RefStore {
         DevBuf d_slices, d_lag, d_out;
-        hipEvent_t done = nullptr;
+        Event done;
         std::atomic<bool> pending{false}; // (_end may run on the caller's bookkeeping thread)
     } ref_store[2];
-    hipStream_t ref_store_stream = nullptr;
+    Stream ref_store_stream;
     // the NEXT chunk, allocated ahead of need by a helper thread (arena_alloc): a hipMalloc of GBs is 30 ms per GB on a box whose
     // VRAM this process touches for the first time -- 150 ms in the middle of a step (profiles/r6/)
     std::future<ArenaChunk> arena_spare;
@@ -96,13 +136,13 @@ struct agc_hip_ctx {
     // the (k1, k2) -> group table (mirror of the host's map_segments) and the work area of agc_hip_segments_packed
     DevBuf d_gmap, d_gmap_stage, d_segwork, d_segtmp;
     uint64_t gmap_slots = 0;
-    void *h_gmap_stage = nullptr; // pinned staging of agc_hip_group_map_update
-    size_t h_gmap_stage_cap = 0;
-    hipEvent_t gmap_ev = nullptr;
+    PinnedBuf h_gmap_stage; // staging of agc_hip_group_map_update
+    Event gmap_ev;
     bool gmap_ev_valid = false;
-    uint32_t *h_zsizes = nullptr; // pinned: frame sizes of the entropy launch in flight (a pageable destination makes the "async" copy
-    size_t h_zsizes_cap = 0;      // wait for the launch inside the call, spinning: a core of the host pool's for the whole launch)
-    void *h_segcounts = nullptr; // pinned: SegCounts of the call in flight (+ 64: the count of the encode launched from them)
+    // frame sizes of the entropy launch in flight (a pageable destination makes the "async" copy wait for the launch inside the call,
+    // spinning: a core of the host pool's for the whole launch)
+    PinnedBuf h_zsizes;
+    PinnedBuf h_segcounts; // SegCounts of the call in flight (+ 64: the count of the encode launched from them)
     // what agc_hip_segments_packed left on the device for agc_hip_segments_encode_known
     struct SegState {
         bool valid = false;
@@ -121,8 +161,8 @@ struct agc_hip_ctx {
     std::mutex host_alloc_mtx; // host_allocs: agc_hip_host_alloc / _free may be called from the thread that collects an encode
     // pinned staging ring of the small host -> device uploads (descriptors, offsets, tables): a copy from pageable memory makes the
     // calling thread wait for the copy engine -- behind whatever else it is moving, e.g. the 22 MB of a sample's deltas
-    uint8_t *up_ring = nullptr;
-    size_t up_cap = 0, up_head = 0;
+    PinnedBuf up_ring;
+    size_t up_head = 0;
     std::mutex up_mtx;
     // the ring in UP_PARTS parts: a part remembers the streams that copied out of it and, when the head leaves it, an event on each;
     // the head waits for those events when it comes back (a ring's length later: they are long done -- the whole-ring wait for
@@ -130,61 +170,58 @@ struct agc_hip_ctx {
     static constexpr int UP_PARTS = 4, UP_STREAMS = 12;
     struct UpPart {
         hipStream_t st[UP_STREAMS] = {};
-        hipEvent_t ev[UP_STREAMS] = {};
+        Event ev[UP_STREAMS];
         int n = 0;         // streams noted since the head came in
         int n_recorded = 0; // events recorded when it left
     } up_part[UP_PARTS];
 
-    // second LZ lane: agc_hip_lz_encode_begin_dev / _end run the encode of a whole sample on `stream2` with their own scratch,
+    // second LZ lane: agc_hip_lz_encode_begin_dev / _end run the encode of a whole sample on the lane's stream with their own scratch,
     // beside the estimates / cost vectors / index builds the caller goes on with on `stream`
     struct Lane2 {
         DevBuf d_segs, d_counter, d_resv, d_resp, d_scratch, d_dstoff, d_compact;
         DevBuf d_n; // the lane's own copy of a segment count made on the device (the work area it came from is re-laid-out by the next sample)
         PackTemp pk;
-        uint32_t *h_lens = nullptr; // pinned (a device-to-host copy into pageable memory would make begin wait for the kernel)
-        size_t h_lens_cap = 0;
+        PinnedBuf h_lens; // (a device-to-host copy into pageable memory would make begin wait for the kernel)
         uint32_t n = 0;          // segments of the encode in flight
         const uint32_t *n_pinned = nullptr; // != nullptr: their number arrives with the parse (descriptors made on the device)
         bool pending = false, timed = false;
-        hipEvent_t e0 = nullptr, e1 = nullptr, ready = nullptr;
+        Event e0, e1, ready;
         // `done`: recorded behind the parse of the encode in flight.  A caller may collect that encode from another thread while
         // this one already works on the next sample (agc_hip_lz_encode_end only touches this lane): whatever overwrites a buffer
         // the parse reads -- the sample staging buffers -- waits for the event on its own stream (sample_buffer, prefetch)
-        hipEvent_t done = nullptr;
+        Event done;
         bool done_valid = false;
-        hipStream_t s = nullptr; // the lane's stream
+        Stream s; // the lane's stream, at the first stream's priority
     } l2, l3; // (l3: a second encode in flight -- the segments of a sample whose group was minted by that very sample, launched at
               // commit time behind the whole-sample encode of l2 and collected by the same bookkeeping task)
-    hipStream_t stream2 = nullptr, stream3 = nullptr;
     Lane2 &lane(int which) { return which == 2 ? l3 : l2; }
 
     // the NEXT sample, started ahead of its turn (agc_hip_prefetch_packed_dev): expansion into one of two staging buffers and the
     // packed splitter scan, on a stream of their own with their own scratch -- they fill the gaps the sample in front leaves on the
     // GPU while the host registers its segments
     struct Prefetch {
-        hipStream_t stream = nullptr;
+        Stream stream;
         DevBuf d_ranges, d_hits, d_counter;
-        uint32_t *h_count = nullptr; // pinned
+        PinnedBuf h_count; // one word
         const void *words = nullptr; // identity of the packed sample in flight
         uint64_t n_symbols = 0;
         uint32_t dev_cap = 0, k = 0, n_ctg = 0;
         uint64_t first_off = 0, last_off = 0;
         bool valid = false, scanned = false;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
+        Event e0, e1;
         bool timed = false;
     } pf;
 
     // agc_hip_pack_fasta_begin / _end: raw FASTA bodies -> the packed sample on a stream of its own (pack_kernels.hip)
     struct PackFasta {
-        hipStream_t stream = nullptr;
+        Stream stream;
         DevBuf d_state, d_rng, d_off; // the three counters; the ranges; n_ctg + 1 symbol offsets + the total
         DevBuf d_tcnt, d_toff;        // two-pass variant: symbols per tile, symbols in front of every tile
-        uint64_t *h_res = nullptr;    // pinned: offsets, total, escaped-block count
-        size_t h_res_cap = 0;
+        PinnedBuf h_res;              // offsets, total, escaped-block count
         uint32_t n_ctg = 0;
         uint64_t n_raw = 0, esc_cap = 0;
         bool pending = false, timed = false;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
+        Event e0, e1;
     } pfa;
 
     // the parse in chunks (launch_parse): chunk list, logs and per-chunk output of the first stream and of the two encode lanes
@@ -198,15 +235,15 @@ struct agc_hip_ctx {
     } chunk_bufs[3];
 
     // pinned host allocations handed out by agc_hip_host_alloc
-    std::vector<void *> host_allocs;
+    std::vector<PinnedBuf> host_allocs;
 
     // timing
     bool timing = false;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, zev0 = nullptr, zev1 = nullptr;
+    Event zev0, zev1; // ZTimer
     // KTimer's event pairs: recorded around a launch and READ LATER (when the ring comes round, or by agc_hip_timing_get) -- timing a
     // run must not add a wait behind every kernel of the steps' stream (rounds 1-5 did: hipEventSynchronize in KTimer's destructor)
     struct TimerPair {
-        hipEvent_t a = nullptr, b = nullptr;
+        Event a, b;
         int which = -1; // >= 0: recorded, not read yet
     };
     std::vector<TimerPair> tpairs;
@@ -233,6 +270,28 @@ struct agc_hip_ctx {
 
 namespace {
 
+// host time between the marks of a call with many items (n > 10000; ~0u: of every call), on stderr under AGC_HIP_LAPS
+struct Laps {
+    const char *who;
+    bool on;
+    double last = 0;
+    static bool enabled()
+    {
+        static const bool e = getenv("AGC_HIP_LAPS") != nullptr;
+        return e;
+    }
+    static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    Laps(const char *who_, uint32_t n) : who(who_), on(enabled() && n > 10000) { last = on ? now() : 0; }
+    void operator()(const char *what)
+    {
+        if (!on)
+            return;
+        const double t = now();
+        fprintf(stderr, "    %s lap %s %.3f ms\n", who, what, t - last);
+        last = t;
+    }
+};
+
 int ensure(agc_hip_ctx *c, DevBuf &b, size_t bytes, hipStream_t stream = nullptr)
 {
     if (bytes <= b.cap)
@@ -243,20 +302,28 @@ int ensure(agc_hip_ctx *c, DevBuf &b, size_t bytes, hipStream_t stream = nullptr
     // hipFree/hipMalloc (hundreds of ms for multi-GB buffers) out of the steady state
     size_t want = std::max(bytes + bytes / 4, b.cap + b.cap / 2);
     want = (want + 255) & ~(size_t)255;
-    static const bool laps = getenv("AGC_HIP_LAPS") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
+    const double t0 = Laps::now();
     const size_t had = b.cap;
     if (b.p) {
         HIPCHK(c, hipStreamSynchronize(stream));
-        HIPCHK(c, hipFree(b.p));
-        b.p = nullptr;
-        b.cap = 0;
+        HIPCHK(c, b.release());
     }
     HIPCHK(c, hipMalloc(&b.p, want));
     b.cap = want;
-    if (laps && want >= ((size_t)16 << 20))
-        fprintf(stderr, "    ensure: a device buffer grows from %.1f to %.1f MB (asked: %.1f) in %.3f ms\n", had / 1e6, want / 1e6, bytes / 1e6,
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    if (Laps::enabled() && want >= ((size_t)16 << 20))
+        fprintf(stderr, "    ensure: a device buffer grows from %.1f to %.1f MB (asked: %.1f) in %.3f ms\n", had / 1e6, want / 1e6, bytes / 1e6, Laps::now() - t0);
+    return AGC_HIP_OK;
+}
+
+// pinned memory of at least `need` bytes in b: what is there, or a new buffer of `alloc` bytes (the headroom is the caller's: every
+// buffer grows by its own rule).  Whatever read or wrote the old one is done: the callers have waited for it.
+int ensure_pinned(agc_hip_ctx *c, PinnedBuf &b, size_t need, size_t alloc)
+{
+    if (need <= b.cap)
+        return AGC_HIP_OK;
+    HIPCHK(c, b.release());
+    HIPCHK(c, hipHostMalloc(&b.p, alloc, hipHostMallocDefault));
+    b.cap = alloc;
     return AGC_HIP_OK;
 }
 
@@ -266,47 +333,44 @@ size_t arena_next_size(const agc_hip_ctx *c)
     // its references, not with their number
     size_t held = 0;
     for (const ArenaChunk &ch : c->arena)
-        held += ch.size;
+        held += ch.mem.cap;
     return std::max((size_t)256 << 20, std::min(held / 2, (size_t)8 << 30));
 }
 
 int arena_alloc(agc_hip_ctx *c, size_t bytes, uint8_t **out)
 {
     bytes = (bytes + 255) & ~(size_t)255;
-    static const bool laps = getenv("AGC_HIP_LAPS") != nullptr;
-    if (c->arena.empty() || c->arena.back().used + bytes > c->arena.back().size) {
-        const auto t0 = std::chrono::steady_clock::now();
-        ArenaChunk nc{nullptr, 0, 0};
+    if (c->arena.empty() || c->arena.back().used + bytes > c->arena.back().mem.cap) {
+        const double t0 = Laps::now();
+        ArenaChunk nc;
         if (c->arena_spare.valid()) { // (allocated since the current chunk was half full: long done)
             nc = c->arena_spare.get();
-            if (nc.p && nc.size < bytes) {
-                (void)hipFree(nc.p);
-                nc = ArenaChunk{nullptr, 0, 0};
-            }
+            if (nc.mem.cap < bytes)
+                nc = ArenaChunk(); // (too small for this request: given back)
         }
-        if (!nc.p) {
+        if (!nc.mem.p) {
             const size_t sz = std::max(bytes, arena_next_size(c));
-            uint8_t *p = nullptr;
-            HIPCHK(c, hipMalloc((void **)&p, sz + 4096)); // tail slack: 16-byte over-reads never leave the allocation
-            nc = ArenaChunk{p, sz, 0};
+            HIPCHK(c, hipMalloc(&nc.mem.p, sz + 4096)); // tail slack: 16-byte over-reads never leave the allocation
+            nc.mem.cap = sz;
         }
-        c->arena.push_back(nc);
-        if (laps)
-            fprintf(stderr, "    arena: a chunk of %.1f MB becomes current in %.3f ms\n", nc.size / 1e6,
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        c->arena.push_back(std::move(nc));
+        if (Laps::enabled())
+            fprintf(stderr, "    arena: a chunk of %.1f MB becomes current in %.3f ms\n", c->arena.back().mem.cap / 1e6, Laps::now() - t0);
     }
     ArenaChunk &ch = c->arena.back();
-    *out = ch.p + ch.used;
+    *out = ch.mem.as<uint8_t>() + ch.used;
     ch.used += bytes;
     // the chunk after this one is asked for as soon as this one is half full, on a thread of its own
-    if (!c->arena_spare.valid() && ch.used * 2 >= ch.size) {
+    if (!c->arena_spare.valid() && ch.used * 2 >= ch.mem.cap) {
         const size_t sz = arena_next_size(c);
         const int dev = c->device;
         c->arena_spare = std::async(std::launch::async, [sz, dev] {
-            uint8_t *p = nullptr;
-            if (hipSetDevice(dev) != hipSuccess || hipMalloc((void **)&p, sz + 4096) != hipSuccess)
-                return ArenaChunk{nullptr, 0, 0}; // (arena_alloc then allocates when the chunk is needed, and reports)
-            return ArenaChunk{p, sz, 0};
+            ArenaChunk sp; // (left empty on failure: arena_alloc then allocates when the chunk is needed, and reports)
+            if (hipSetDevice(dev) == hipSuccess && hipMalloc(&sp.mem.p, sz + 4096) == hipSuccess)
+                sp.mem.cap = sz;
+            else
+                sp.mem.p = nullptr;
+            return sp;
         });
     }
     return AGC_HIP_OK;
@@ -343,7 +407,7 @@ struct KTimer {
         p = &c->tpairs[c->tpair_next];
         c->tpair_next = (c->tpair_next + 1) % c->tpairs.size();
         ktimer_read(c, *p); // (a pair recorded 256 launches ago: long done)
-        if ((!p->a && hipEventCreate(&p->a) != hipSuccess) || (!p->b && hipEventCreate(&p->b) != hipSuccess)) {
+        if ((!p->a && hipEventCreate(&p->a.h) != hipSuccess) || (!p->b && hipEventCreate(&p->b.h) != hipSuccess)) {
             p = nullptr;
             return;
         }
@@ -355,28 +419,6 @@ struct KTimer {
             (void)hipEventRecord(p->b, c->stream);
             p->which = which;
         }
-    }
-};
-
-// host time between the marks of a call with many items (n > 10000), on stderr under AGC_HIP_LAPS
-struct Laps {
-    const char *who;
-    bool on;
-    double last = 0;
-    static bool enabled()
-    {
-        static const bool e = getenv("AGC_HIP_LAPS") != nullptr;
-        return e;
-    }
-    static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-    Laps(const char *who_, uint32_t n) : who(who_), on(enabled() && n > 10000) { last = on ? now() : 0; }
-    void operator()(const char *what)
-    {
-        if (!on)
-            return;
-        const double t = now();
-        fprintf(stderr, "    %s lap %s %.3f ms\n", who, what, t - last);
-        last = t;
     }
 };
 
@@ -409,17 +451,14 @@ int upload_piece(agc_hip_ctx *c, void *d_dst, const void *h_src, size_t bytes, h
     // (the lock is held until the copy is queued: the event a part records on a stream when the head leaves is then behind every
     // copy out of that part)
     std::lock_guard<std::mutex> lk(c->up_mtx);
-    if (!c->up_ring) {
-        HIPCHK(c, hipHostMalloc((void **)&c->up_ring, RING, hipHostMallocDefault));
-        c->up_cap = RING;
-    }
+    CHK(ensure_pinned(c, c->up_ring, RING, RING));
     const size_t need = (bytes + 255) & ~(size_t)255;
     size_t part = c->up_head ? (c->up_head - 1) / PART : 0; // (a head at a part's very end still belongs to it)
     if (c->up_head + need > (part + 1) * PART) {
         agc_hip_ctx::UpPart &old_part = c->up_part[part];
         for (int i = 0; i < old_part.n; ++i) {
             if (!old_part.ev[i])
-                HIPCHK(c, hipEventCreateWithFlags(&old_part.ev[i], hipEventDisableTiming));
+                HIPCHK(c, hipEventCreateWithFlags(&old_part.ev[i].h, hipEventDisableTiming));
             HIPCHK(c, hipEventRecord(old_part.ev[i], old_part.st[i]));
         }
         old_part.n_recorded = old_part.n;
@@ -442,7 +481,7 @@ int upload_piece(agc_hip_ctx *c, void *d_dst, const void *h_src, size_t bytes, h
         } else
             P.st[P.n++] = st;
     }
-    uint8_t *slot = c->up_ring + c->up_head;
+    uint8_t *slot = c->up_ring.as<uint8_t>() + c->up_head;
     c->up_head += need;
     std::memcpy(slot, h_src, bytes);
     HIPCHK(c, hipMemcpyAsync(d_dst, slot, bytes, hipMemcpyHostToDevice, st));
@@ -475,6 +514,23 @@ hipError_t create_low_priority_stream(hipStream_t *s)
     if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess)
         return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
     return hipStreamCreateWithPriority(s, hipStreamNonBlocking, lo);
+}
+
+// what agc_hip_create makes at once (everything else is made by the entry point that first needs it).  The entropy stage: two
+// low-priority streams, the events that order them, and the one its caller sleeps on
+bool make_entropy_lane(agc_hip_ctx *c)
+{
+    return create_low_priority_stream(&c->zstream.h) == hipSuccess && create_low_priority_stream(&c->zstream2.h) == hipSuccess &&
+           hipEventCreateWithFlags(&c->zev_a.h, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&c->zev_b.h, hipEventDisableTiming) == hipSuccess &&
+           hipEventCreateWithFlags(&c->zev_wait.h, hipEventDisableTiming | hipEventBlockingSync) == hipSuccess;
+}
+
+// An encode lane, at the first stream's priority: measured with a low-priority lane the whole-sample encode is starved by the
+// classification kernels until they are done and ends up on the critical path of the NEXT sample's launch
+bool make_encode_lane(agc_hip_ctx::Lane2 &L)
+{
+    return hipStreamCreateWithFlags(&L.s.h, hipStreamNonBlocking) == hipSuccess && hipEventCreate(&L.e0.h) == hipSuccess && hipEventCreate(&L.e1.h) == hipSuccess &&
+           hipEventCreateWithFlags(&L.ready.h, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&L.done.h, hipEventDisableTiming) == hipSuccess;
 }
 
 int upload_refs(agc_hip_ctx *c)
@@ -674,25 +730,11 @@ int agc_hip_create(agc_hip_ctx **out, int device)
         return AGC_HIP_ENODEV;
     agc_hip_ctx *c = new agc_hip_ctx();
     c->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        create_low_priority_stream(&c->zstream) != hipSuccess || create_low_priority_stream(&c->zstream2) != hipSuccess ||
-        hipEventCreateWithFlags(&c->zev_a, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->zev_b, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->zev_wait, hipEventDisableTiming | hipEventBlockingSync) != hipSuccess ||
-        // (the second lane at the first stream's priority: measured with a low-priority lane the whole-sample encode is starved by
-        // the classification kernels until they are done and ends up on the critical path of the NEXT sample's launch)
-        hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&c->l2.e0) != hipSuccess ||
-        hipEventCreate(&c->l2.e1) != hipSuccess || hipEventCreateWithFlags(&c->l2.ready, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->l2.done, hipEventDisableTiming) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&c->l3.e0) != hipSuccess ||
-        hipEventCreate(&c->l3.e1) != hipSuccess || hipEventCreateWithFlags(&c->l3.ready, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->l3.done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreate(&c->ev0) != hipSuccess ||
-        hipEventCreate(&c->ev1) != hipSuccess || hipEventCreate(&c->zev0) != hipSuccess || hipEventCreate(&c->zev1) != hipSuccess) {
-        delete c;
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream.h, hipStreamNonBlocking) != hipSuccess || !make_entropy_lane(c) ||
+        !make_encode_lane(c->l2) || !make_encode_lane(c->l3) || hipEventCreate(&c->zev0.h) != hipSuccess || hipEventCreate(&c->zev1.h) != hipSuccess) {
+        delete c; // (releases what was made)
         return AGC_HIP_ENODEV;
     }
-    c->l2.s = c->stream2;
-    c->l3.s = c->stream3;
     *out = c;
     return AGC_HIP_OK;
 }
@@ -702,127 +744,17 @@ void agc_hip_destroy(agc_hip_ctx *c)
     if (!c)
         return;
     (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    if (c->zstream)
-        (void)hipStreamSynchronize(c->zstream);
-    if (c->zstream2)
-        (void)hipStreamSynchronize(c->zstream2);
-    for (hipStream_t s_ : {c->stream2, c->stream3})
+    // Every stream the context has made runs dry and both helper threads hand over what they allocated BEFORE the first member
+    // goes: nothing on the device or on a thread refers to a member any more, so the order in which the members' destructors run
+    // does not matter.
+    for (hipStream_t s_ : {c->stream.h, c->zstream.h, c->zstream2.h, c->l2.s.h, c->l3.s.h, c->pfa.stream.h, c->pf.stream.h, c->ref_store_stream.h})
         if (s_)
             (void)hipStreamSynchronize(s_);
+    if (c->arena_spare.valid())
+        (void)c->arena_spare.get();
     for (auto &cb : c->chunk_bufs)
-        for (DevBuf *b : {&cb.d_jobs, &cb.d_seg0, &cb.d_logs, &cb.d_logn, &cb.d_out})
-            if (b->p)
-                (void)hipFree(b->p);
-    if (c->pfa.stream) {
-        (void)hipStreamSynchronize(c->pfa.stream);
-        (void)hipStreamDestroy(c->pfa.stream);
-        for (DevBuf *b : {&c->pfa.d_state, &c->pfa.d_rng, &c->pfa.d_off, &c->pfa.d_tcnt, &c->pfa.d_toff})
-            if (b->p)
-                (void)hipFree(b->p);
-        if (c->pfa.h_res)
-            (void)hipHostFree(c->pfa.h_res);
-        if (c->pfa.e0)
-            (void)hipEventDestroy(c->pfa.e0);
-        if (c->pfa.e1)
-            (void)hipEventDestroy(c->pfa.e1);
-    }
-    if (c->pf.stream) {
-        (void)hipStreamSynchronize(c->pf.stream);
-        (void)hipStreamDestroy(c->pf.stream);
-        (void)hipHostFree(c->pf.h_count);
-        (void)hipEventDestroy(c->pf.e0);
-        (void)hipEventDestroy(c->pf.e1);
-        for (DevBuf *b : {&c->pf.d_ranges, &c->pf.d_hits, &c->pf.d_counter})
-            if (b->p)
-                (void)hipFree(b->p);
-    }
-    for (void *hp : c->host_allocs)
-        (void)hipHostFree(hp);
-    if (c->up_ring)
-        (void)hipHostFree(c->up_ring);
-    for (auto &up : c->up_part)
-        for (hipEvent_t e : up.ev)
-            if (e)
-                (void)hipEventDestroy(e);
-    for (auto *ln : {&c->l2, &c->l3})
-        if (ln->h_lens)
-            (void)hipHostFree(ln->h_lens);
-    DevBuf *bufs[] = {&c->d_table, &c->d_bloom, &c->d_bloom2, &c->d_sbloom, &c->d_refs, &c->d_ranges, &c->d_hits, &c->d_counter, &c->d_segs, &c->d_slices,
-                      &c->d_scratch, &c->d_resv, &c->d_resp, &c->d_dstoff, &c->d_compact, &c->d_jobs, &c->d_counts,
-                      &c->d_in, &c->d_pp_cnt, &c->d_pp_off, &c->d_pp_total, &c->d_lag, &c->d_sample, &c->d_zsrc, &c->d_zdst, &c->d_zws,
-                      &c->d_zjobs, &c->d_zsize, &c->d_zout, &c->d_zdstoff, &c->d_maybe, &c->d_fjobs, &c->d_dec_enc, &c->d_dec_jobs, &c->d_dec_res, &c->d_dec_out,
-                      &c->l2.d_segs, &c->l2.d_counter, &c->l2.d_resv, &c->l2.d_resp, &c->l2.d_scratch, &c->l2.d_dstoff,
-                      &c->l2.d_compact, &c->l3.d_segs, &c->l3.d_counter, &c->l3.d_resv, &c->l3.d_resp, &c->l3.d_scratch, &c->l3.d_dstoff,
-                      &c->l3.d_compact, &c->l2.d_n, &c->l3.d_n, &c->d_esc_jobs, &c->d_flags, &c->d_gmap, &c->d_gmap_stage, &c->d_segwork, &c->d_segtmp};
-    if (c->h_segcounts)
-        (void)hipHostFree(c->h_segcounts);
-    if (c->h_zsizes)
-        (void)hipHostFree(c->h_zsizes);
-    if (c->h_gmap_stage)
-        (void)hipHostFree(c->h_gmap_stage);
-    if (c->gmap_ev)
-        (void)hipEventDestroy(c->gmap_ev);
-    for (PackTemp *t : {&c->pk1, &c->pk_sample, &c->l2.pk, &c->l3.pk})
-        for (DevBuf *b : {&t->words, &t->index, &t->esc, &t->cnt})
-            if (b->p)
-                (void)hipFree(b->p);
-    for (DevBuf *b : bufs)
-        if (b->p)
-            (void)hipFree(b->p);
-    for (auto &ch : c->arena)
-        (void)hipFree(ch.p);
-    for (auto &cbufs : c->chunk_bufs)
-        if (cbufs.logs_ahead.valid()) {
-            const DevBuf ahead = cbufs.logs_ahead.get();
-            if (ahead.p)
-                (void)hipFree(ahead.p);
-        }
-    for (auto &rs : c->ref_store) {
-        for (DevBuf *b : {&rs.d_slices, &rs.d_lag, &rs.d_out})
-            if (b->p)
-                (void)hipFree(b->p);
-        if (rs.done)
-            (void)hipEventDestroy(rs.done);
-    }
-    if (c->ref_store_stream) {
-        (void)hipStreamSynchronize(c->ref_store_stream);
-        (void)hipStreamDestroy(c->ref_store_stream);
-    }
-    if (c->arena_spare.valid()) {
-        const ArenaChunk sp = c->arena_spare.get();
-        if (sp.p)
-            (void)hipFree(sp.p);
-    }
-    for (auto &tp : c->tpairs) {
-        if (tp.a)
-            (void)hipEventDestroy(tp.a);
-        if (tp.b)
-            (void)hipEventDestroy(tp.b);
-    }
-    if (c->ev0)
-        (void)hipEventDestroy(c->ev0);
-    if (c->ev1)
-        (void)hipEventDestroy(c->ev1);
-    if (c->zev0)
-        (void)hipEventDestroy(c->zev0);
-    if (c->zev1)
-        (void)hipEventDestroy(c->zev1);
-    if (c->stream)
-        (void)hipStreamDestroy(c->stream);
-    if (c->zstream)
-        (void)hipStreamDestroy(c->zstream);
-    if (c->zstream2)
-        (void)hipStreamDestroy(c->zstream2);
-    for (hipEvent_t e : {c->zev_a, c->zev_b, c->zev_wait})
-        if (e)
-            (void)hipEventDestroy(e);
-    for (hipEvent_t e : {c->l2.e0, c->l2.e1, c->l2.ready, c->l2.done, c->l3.e0, c->l3.e1, c->l3.ready, c->l3.done})
-        if (e)
-            (void)hipEventDestroy(e);
-    for (hipStream_t s_ : {c->stream2, c->stream3})
-        if (s_)
-            (void)hipStreamDestroy(s_);
+        if (cb.logs_ahead.valid())
+            (void)cb.logs_ahead.get();
     delete c;
 }
 
@@ -1259,9 +1191,9 @@ int agc_hip_pack_fasta_begin(agc_hip_ctx *c, const uint8_t *d_raw, uint64_t n_ra
     HIPCHK(c, hipSetDevice(c->device));
     agc_hip_ctx::PackFasta &P = c->pfa;
     if (!P.stream) {
-        HIPCHK(c, hipStreamCreateWithFlags(&P.stream, hipStreamNonBlocking));
-        HIPCHK(c, hipEventCreate(&P.e0));
-        HIPCHK(c, hipEventCreate(&P.e1));
+        HIPCHK(c, hipStreamCreateWithFlags(&P.stream.h, hipStreamNonBlocking));
+        HIPCHK(c, hipEventCreate(&P.e0.h));
+        HIPCHK(c, hipEventCreate(&P.e1.h));
     }
     if (P.pending) { // (a pack nobody collected: dropped)
         HIPCHK(c, hipStreamSynchronize(P.stream));
@@ -1271,14 +1203,8 @@ int agc_hip_pack_fasta_begin(agc_hip_ctx *c, const uint8_t *d_raw, uint64_t n_ra
     P.n_raw = n_raw;
     P.esc_cap = esc_cap_blocks;
     const size_t res_words = (size_t)n_ctg + 4;
-    if (P.h_res_cap < res_words) {
-        if (P.h_res)
-            HIPCHK(c, hipHostFree(P.h_res));
-        P.h_res = nullptr;
-        P.h_res_cap = 0;
-        HIPCHK(c, hipHostMalloc((void **)&P.h_res, (res_words + 1024) * 8, hipHostMallocDefault));
-        P.h_res_cap = res_words + 1024;
-    }
+    CHK(ensure_pinned(c, P.h_res, res_words * 8, (res_words + 1024) * 8));
+    uint64_t *const h_res = P.h_res.as<uint64_t>();
     const uint32_t n_tiles = (uint32_t)n_tiles64;
     // the counters: [4, 8) escaped blocks, [8, 16) the total
     CHK(ensure(c, P.d_state, 64, P.stream));
@@ -1329,8 +1255,8 @@ int agc_hip_pack_fasta_begin(agc_hip_ctx *c, const uint8_t *d_raw, uint64_t n_ra
     }
     if (P.timed)
         (void)hipEventRecord(P.e1, P.stream);
-    HIPCHK(c, hipMemcpyAsync(P.h_res, P.d_off.p, ((size_t)n_ctg + 1) * 8, hipMemcpyDeviceToHost, P.stream));
-    HIPCHK(c, hipMemcpyAsync(P.h_res + n_ctg + 1, P.d_state.p, 16, hipMemcpyDeviceToHost, P.stream));
+    HIPCHK(c, hipMemcpyAsync(h_res, P.d_off.p, ((size_t)n_ctg + 1) * 8, hipMemcpyDeviceToHost, P.stream));
+    HIPCHK(c, hipMemcpyAsync(h_res + n_ctg + 1, P.d_state.p, 16, hipMemcpyDeviceToHost, P.stream));
     P.pending = true;
     return AGC_HIP_OK;
 }
@@ -1353,10 +1279,11 @@ int agc_hip_pack_fasta_end(agc_hip_ctx *c, uint64_t *h_ctg_off, uint64_t *h_n_es
         P.timed = false;
     }
     const uint32_t n = P.n_ctg;
-    const uint32_t *cnt = (const uint32_t *)(P.h_res + n + 1); // (unused), escaped blocks; the total in the next 8 bytes
-    const uint64_t total = (P.n_raw && n) ? P.h_res[n + 2] : 0;
+    const uint64_t *const h_res = P.h_res.as<uint64_t>();
+    const uint32_t *cnt = (const uint32_t *)(h_res + n + 1); // (unused), escaped blocks; the total in the next 8 bytes
+    const uint64_t total = (P.n_raw && n) ? h_res[n + 2] : 0;
     for (uint32_t i = 0; i < n; ++i) // (a contig whose first byte no tile holds -- it begins at the end of the buffer -- is empty and begins at the total)
-        h_ctg_off[i] = P.h_res[i] == ~0ULL ? total : P.h_res[i];
+        h_ctg_off[i] = h_res[i] == ~0ULL ? total : h_res[i];
     h_ctg_off[n] = total;
     *h_n_esc_blocks = (P.n_raw && n) ? cnt[1] : 0;
     return *h_n_esc_blocks > P.esc_cap ? AGC_HIP_ECAP : AGC_HIP_OK;
@@ -1459,6 +1386,60 @@ static int sbloom_upload(agc_hip_ctx *c, uint32_t k)
 
 } // extern "C"
 
+// the ranges of the 2-bit scan: the contigs of at least k symbols in pieces of about range_len symbols whose inner boundaries are
+// multiples of PACK_BLOCK in the buffer
+static int packed_ranges(const uint64_t *h_ctg_off, uint32_t n_ctg, uint32_t k, uint64_t total, std::vector<ScanRange> &out)
+{
+    const uint64_t target_waves = 4096ULL * 4;
+    uint64_t range_len = (total / target_waves + PACK_BLOCK - 1) / PACK_BLOCK * PACK_BLOCK;
+    range_len = std::min<uint64_t>(std::max<uint64_t>(range_len, 8 * PACK_BLOCK), 256 * PACK_BLOCK);
+    for (uint32_t ci = 0; ci < n_ctg; ++ci) {
+        const uint64_t b = h_ctg_off[ci], e = h_ctg_off[ci + 1];
+        if (e < b)
+            return AGC_HIP_EINVAL;
+        if (e - b < k)
+            continue;
+        for (uint64_t p = b; p < e;) {
+            uint64_t q = (p + range_len) & ~(uint64_t)(PACK_BLOCK - 1);
+            if (q >= e || e - q < PACK_BLOCK)
+                q = e;
+            out.push_back({b, e, p, q});
+            p = q;
+        }
+    }
+    return AGC_HIP_OK;
+}
+
+// the packed scan of n_ranges ranges (in `ranges`) queued on `st`: up to dev_cap raw hits into `hits`, their number -- which may be
+// larger -- into the word at `counter`, which the caller has cleared on `st`.  timer_slot: KTimer's row (< 0: not timed)
+static int launch_packed_scan(agc_hip_ctx *c, const PackedView &pv, const DevBuf &ranges, uint32_t n_ranges, uint32_t k, const DevBuf &hits, const DevBuf &counter,
+                              uint32_t dev_cap, hipStream_t st, int timer_slot)
+{
+    if (!c->lds_scan_set) {
+        HIPCHK(c, hipFuncSetAttribute((const void *)scan_packed_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SBLOOM_WORDS * 4));
+        c->lds_scan_set = true;
+    }
+    ScanPackedArgs a;
+    a.pv = pv;
+    a.ranges = (const ScanRange *)ranges.p;
+    a.n_ranges = n_ranges;
+    a.k = k;
+    a.table = (const uint64_t *)c->d_table.p;
+    a.table_mask = c->table_mask;
+    a.sbloom = (const uint32_t *)c->d_sbloom.p;
+    a.bloom2 = (const uint32_t *)c->d_bloom2.p;
+    a.hits = (ScanHit *)hits.p;
+    a.n_hits = (uint32_t *)counter.p;
+    a.cap = dev_cap;
+    const uint32_t grid = grid_for(n_ranges, 16, 256); // one 1024-thread block per CU (128 KiB of LDS each)
+    {
+        KTimer t(c, timer_slot);
+        hipLaunchKernelGGL(scan_packed_kernel, dim3(grid), dim3(1024), SBLOOM_WORDS * 4, st, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    return AGC_HIP_OK;
+}
+
 // the packed splitter scan of a sample on the context's stream: raw hits (unsorted, before the reset rule) in c->d_hits
 static int packed_scan_raw(agc_hip_ctx *c, const agc_hip_packed *pk, const uint64_t *h_ctg_off, uint32_t n_ctg, uint32_t k, uint32_t *n_found_out)
 {
@@ -1471,25 +1452,8 @@ static int packed_scan_raw(agc_hip_ctx *c, const agc_hip_packed *pk, const uint6
     if (!pk->d_words || !pk->d_esc_index || h_ctg_off[n_ctg] > pk->n_symbols)
         return AGC_HIP_EINVAL;
     CHK(sbloom_upload(c, k));
-    // ranges: pieces of about range_len symbols whose inner boundaries are multiples of PACK_BLOCK in the buffer
-    const uint64_t target_waves = 4096ULL * 4;
-    uint64_t range_len = (total / target_waves + PACK_BLOCK - 1) / PACK_BLOCK * PACK_BLOCK;
-    range_len = std::min<uint64_t>(std::max<uint64_t>(range_len, 8 * PACK_BLOCK), 256 * PACK_BLOCK);
     std::vector<ScanRange> ranges;
-    for (uint32_t ci = 0; ci < n_ctg; ++ci) {
-        const uint64_t b = h_ctg_off[ci], e = h_ctg_off[ci + 1];
-        if (e < b)
-            return AGC_HIP_EINVAL;
-        if (e - b < k)
-            continue;
-        for (uint64_t p = b; p < e;) {
-            uint64_t q = (p + range_len) & ~(uint64_t)(PACK_BLOCK - 1);
-            if (q >= e || e - q < PACK_BLOCK)
-                q = e;
-            ranges.push_back({b, e, p, q});
-            p = q;
-        }
-    }
+    CHK(packed_ranges(h_ctg_off, n_ctg, k, total, ranges));
     if (ranges.empty())
         return AGC_HIP_OK;
     if (ranges.size() > 0x7fffffffULL)
@@ -1497,33 +1461,13 @@ static int packed_scan_raw(agc_hip_ctx *c, const agc_hip_packed *pk, const uint6
     CHK(ensure(c, c->d_ranges, ranges.size() * sizeof(ScanRange)));
     CHK(ensure(c, c->d_counter, 64));
     CHK(upload(c, c->d_ranges.p, ranges.data(), ranges.size() * sizeof(ScanRange), c->stream));
-    if (!c->lds_scan_set) {
-        HIPCHK(c, hipFuncSetAttribute((const void *)scan_packed_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SBLOOM_WORDS * 4));
-        c->lds_scan_set = true;
-    }
+    const PackedView pv = {pk->d_words, pk->d_esc_index, pk->d_esc_bytes, pk->n_symbols};
     uint32_t dev_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(total / 2000 + 4096, c->d_hits.cap / sizeof(ScanHit)), 1u << 30);
     uint32_t n_found = 0;
-    for (int attempt = 0; attempt < 2; ++attempt) {
+    for (int attempt = 0; attempt < 2; ++attempt) { // (more hits than the list held: once more, with room for as many as were counted)
         CHK(ensure(c, c->d_hits, (size_t)dev_cap * sizeof(ScanHit)));
         HIPCHK(c, hipMemsetAsync(c->d_counter.p, 0, 4, c->stream));
-        ScanPackedArgs a;
-        a.pv = {pk->d_words, pk->d_esc_index, pk->d_esc_bytes, pk->n_symbols};
-        a.ranges = (const ScanRange *)c->d_ranges.p;
-        a.n_ranges = (uint32_t)ranges.size();
-        a.k = k;
-        a.table = (const uint64_t *)c->d_table.p;
-        a.table_mask = c->table_mask;
-        a.sbloom = (const uint32_t *)c->d_sbloom.p;
-        a.bloom2 = (const uint32_t *)c->d_bloom2.p;
-        a.hits = (ScanHit *)c->d_hits.p;
-        a.n_hits = (uint32_t *)c->d_counter.p;
-        a.cap = dev_cap;
-        const uint32_t grid = grid_for((uint32_t)ranges.size(), 16, 256); // one 1024-thread block per CU (128 KiB of LDS each)
-        {
-            KTimer t(c, AGC_HIP_K_SCAN);
-            hipLaunchKernelGGL(scan_packed_kernel, dim3(grid), dim3(1024), SBLOOM_WORDS * 4, c->stream, a);
-        }
-        HIPCHK(c, hipGetLastError());
+        CHK(launch_packed_scan(c, pv, c->d_ranges, (uint32_t)ranges.size(), k, c->d_hits, c->d_counter, dev_cap, c->stream, AGC_HIP_K_SCAN));
         HIPCHK(c, hipMemcpyAsync(&n_found, c->d_counter.p, 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (n_found <= dev_cap)
@@ -1531,6 +1475,26 @@ static int packed_scan_raw(agc_hip_ctx *c, const agc_hip_packed *pk, const uint6
         dev_cap = n_found;
     }
     *n_found_out = n_found;
+    return AGC_HIP_OK;
+}
+
+// The prefetch of this very sample, collected: AGC_HIP_EINVAL when nothing, or something else, was prefetched; otherwise its stream
+// is waited for and its time booked on the scan row.  Then c->pf.scanned, *h_count, dev_cap and d_hits say what it found.
+static int collect_prefetch(agc_hip_ctx *c, const agc_hip_packed *pk, const uint64_t *h_ctg_off, uint32_t n_ctg, uint32_t k)
+{
+    agc_hip_ctx::Prefetch &pf = c->pf;
+    if (!pf.valid || pf.words != pk->d_words || pf.n_symbols != pk->n_symbols || pf.k != k || pf.n_ctg != n_ctg || pf.first_off != h_ctg_off[0] ||
+        pf.last_off != h_ctg_off[n_ctg])
+        return AGC_HIP_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(pf.stream));
+    if (pf.timed) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, pf.e0, pf.e1);
+        c->ms[AGC_HIP_K_SCAN] += ms;
+        c->launches[AGC_HIP_K_SCAN] += 1;
+        pf.timed = false;
+    }
     return AGC_HIP_OK;
 }
 
@@ -1561,10 +1525,10 @@ int agc_hip_prefetch_packed_dev(agc_hip_ctx *c, const agc_hip_packed *pk, const 
     HIPCHK(c, hipSetDevice(c->device));
     agc_hip_ctx::Prefetch &pf = c->pf;
     if (!pf.stream) {
-        HIPCHK(c, hipStreamCreateWithFlags(&pf.stream, hipStreamNonBlocking));
-        HIPCHK(c, hipHostMalloc((void **)&pf.h_count, 64, hipHostMallocDefault));
-        HIPCHK(c, hipEventCreate(&pf.e0));
-        HIPCHK(c, hipEventCreate(&pf.e1));
+        HIPCHK(c, hipStreamCreateWithFlags(&pf.stream.h, hipStreamNonBlocking));
+        CHK(ensure_pinned(c, pf.h_count, 64, 64));
+        HIPCHK(c, hipEventCreate(&pf.e0.h));
+        HIPCHK(c, hipEventCreate(&pf.e1.h));
     }
     HIPCHK(c, hipStreamSynchronize(pf.stream)); // (a prefetch nobody asked for again: its kernels must be done before its buffers go)
     pf.valid = false;
@@ -1575,28 +1539,13 @@ int agc_hip_prefetch_packed_dev(agc_hip_ctx *c, const agc_hip_packed *pk, const 
     pf.timed = c->timing;
     if (pf.timed)
         HIPCHK(c, hipEventRecord(pf.e0, pf.stream));
-    // the scan: as agc_hip_scan_packed_dev, own scratch, nothing waited for
+    // the scan: as packed_scan_raw, own scratch, nothing waited for -- and one attempt: a hit list that overflows (it has twice the
+    // ordinary room per symbol) is found out by whoever collects the prefetch, who scans again the ordinary way
     const uint64_t total = h_ctg_off[n_ctg] - h_ctg_off[0];
-    const uint64_t target_waves = 4096ULL * 4;
-    uint64_t range_len = (total / target_waves + PACK_BLOCK - 1) / PACK_BLOCK * PACK_BLOCK;
-    range_len = std::min<uint64_t>(std::max<uint64_t>(range_len, 8 * PACK_BLOCK), 256 * PACK_BLOCK);
     std::vector<ScanRange> ranges;
-    for (uint32_t ci = 0; ci < n_ctg; ++ci) {
-        const uint64_t b = h_ctg_off[ci], e = h_ctg_off[ci + 1];
-        if (e < b)
-            return AGC_HIP_EINVAL;
-        if (e - b < k)
-            continue;
-        for (uint64_t p = b; p < e;) {
-            uint64_t q = (p + range_len) & ~(uint64_t)(PACK_BLOCK - 1);
-            if (q >= e || e - q < PACK_BLOCK)
-                q = e;
-            ranges.push_back({b, e, p, q});
-            p = q;
-        }
-    }
+    CHK(packed_ranges(h_ctg_off, n_ctg, k, total, ranges));
     pf.scanned = !ranges.empty() && ranges.size() <= 0x7fffffffULL;
-    *pf.h_count = 0;
+    *pf.h_count.as<uint32_t>() = 0;
     if (pf.scanned) {
         CHK(ensure(c, pf.d_ranges, ranges.size() * sizeof(ScanRange), pf.stream));
         CHK(ensure(c, pf.d_counter, 64, pf.stream));
@@ -1604,26 +1553,8 @@ int agc_hip_prefetch_packed_dev(agc_hip_ctx *c, const agc_hip_packed *pk, const 
         CHK(ensure(c, pf.d_hits, (size_t)pf.dev_cap * sizeof(ScanHit), pf.stream));
         CHK(upload(c, pf.d_ranges.p, ranges.data(), ranges.size() * sizeof(ScanRange), pf.stream));
         HIPCHK(c, hipMemsetAsync(pf.d_counter.p, 0, 4, pf.stream));
-        if (!c->lds_scan_set) {
-            HIPCHK(c, hipFuncSetAttribute((const void *)scan_packed_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SBLOOM_WORDS * 4));
-            c->lds_scan_set = true;
-        }
-        ScanPackedArgs a;
-        a.pv = pv;
-        a.ranges = (const ScanRange *)pf.d_ranges.p;
-        a.n_ranges = (uint32_t)ranges.size();
-        a.k = k;
-        a.table = (const uint64_t *)c->d_table.p;
-        a.table_mask = c->table_mask;
-        a.sbloom = (const uint32_t *)c->d_sbloom.p;
-        a.bloom2 = (const uint32_t *)c->d_bloom2.p;
-        a.hits = (ScanHit *)pf.d_hits.p;
-        a.n_hits = (uint32_t *)pf.d_counter.p;
-        a.cap = pf.dev_cap;
-        const uint32_t grid = grid_for((uint32_t)ranges.size(), 16, 256);
-        hipLaunchKernelGGL(scan_packed_kernel, dim3(grid), dim3(1024), SBLOOM_WORDS * 4, pf.stream, a);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(pf.h_count, pf.d_counter.p, 4, hipMemcpyDeviceToHost, pf.stream));
+        CHK(launch_packed_scan(c, pv, pf.d_ranges, (uint32_t)ranges.size(), k, pf.d_hits, pf.d_counter, pf.dev_cap, pf.stream, -1));
+        HIPCHK(c, hipMemcpyAsync(pf.h_count.p, pf.d_counter.p, 4, hipMemcpyDeviceToHost, pf.stream));
     }
     if (pf.timed)
         HIPCHK(c, hipEventRecord(pf.e1, pf.stream));
@@ -1642,23 +1573,12 @@ int agc_hip_scan_prefetched(agc_hip_ctx *c, const agc_hip_packed *pk, const uint
 {
     if (!c || !pk || !h_ctg_off || !h_n_hits)
         return AGC_HIP_EINVAL;
-    agc_hip_ctx::Prefetch &pf = c->pf;
-    if (!pf.valid || pf.words != pk->d_words || pf.n_symbols != pk->n_symbols || pf.k != k || pf.n_ctg != n_ctg || pf.first_off != h_ctg_off[0] ||
-        pf.last_off != h_ctg_off[n_ctg])
-        return AGC_HIP_EINVAL; // nothing, or something else, was prefetched
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(pf.stream));
-    if (pf.timed) { // (the prefetched scan: the scan row)
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, pf.e0, pf.e1);
-        c->ms[AGC_HIP_K_SCAN] += ms;
-        c->launches[AGC_HIP_K_SCAN] += 1;
-        pf.timed = false;
-    }
+    CHK(collect_prefetch(c, pk, h_ctg_off, n_ctg, k));
+    const agc_hip_ctx::Prefetch &pf = c->pf;
     *h_n_hits = 0;
     if (!pf.scanned)
         return AGC_HIP_OK;
-    const uint32_t n_found = *pf.h_count;
+    const uint32_t n_found = *pf.h_count.as<uint32_t>();
     if (n_found > pf.dev_cap) // (more hits than the list held: the scan again, the ordinary way)
         return agc_hip_scan_packed_dev(c, pk, h_ctg_off, n_ctg, k, cap, h_n_hits, h_hit_ctg, h_hit_pos, h_hit_dir, h_hit_rc);
     return deliver_hits(c, n_found, h_ctg_off, n_ctg, k, cap, h_n_hits, h_hit_ctg, h_hit_pos, h_hit_dir, h_hit_rc, pf.d_hits.p, pf.stream);
@@ -2090,15 +2010,12 @@ int launch_parse(agc_hip_ctx *c, uint32_t n, uint8_t *out_bytes, uint32_t *out_u
             CHK(ensure(c, cb.d_jobs, jobs.size() * sizeof(ChunkJob), st));
             CHK(ensure(c, cb.d_seg0, seg0.size() * 4, st));
             if (cb.logs_ahead.valid()) { // (allocated ahead by a helper thread: see ChunkBufs)
-                const DevBuf ahead = cb.logs_ahead.get();
-                if (ahead.p && ahead.cap > cb.d_logs.cap) {
-                    if (cb.d_logs.p) {
+                DevBuf ahead = cb.logs_ahead.get();
+                if (ahead.p && ahead.cap > cb.d_logs.cap) { // (otherwise it goes back as `ahead` goes)
+                    if (cb.d_logs.p)
                         HIPCHK(c, hipStreamSynchronize(st));
-                        HIPCHK(c, hipFree(cb.d_logs.p));
-                    }
-                    cb.d_logs = ahead;
-                } else if (ahead.p)
-                    (void)hipFree(ahead.p);
+                    cb.d_logs = std::move(ahead);
+                }
             }
             CHK(ensure(c, cb.d_logs, jobs.size() * (size_t)pl.cap * sizeof(ChunkState), st));
             CHK(ensure(c, cb.d_logn, jobs.size() * 4, st));
@@ -2112,10 +2029,10 @@ int launch_parse(agc_hip_ctx *c, uint32_t n, uint8_t *out_bytes, uint32_t *out_u
             pl.log_n = (uint32_t *)cb.d_logn.p;
             pl.chunk_out = (uint8_t *)cb.d_out.p;
             static const bool chunk_log = getenv("AGC_HIP_CHUNK_LOG") != nullptr; // (a measuring aid: every chunked launch on stderr)
-            hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+            Event ev[3];
             if (chunk_log)
                 for (auto &e : ev)
-                    (void)hipEventCreate(&e);
+                    (void)hipEventCreate(&e.h);
             {
                 KTimer t(c, lane ? -1 : MODE == MODE_ENCODE ? AGC_HIP_K_ENCODE : MODE == MODE_ESTIMATE ? AGC_HIP_K_ESTIMATE : AGC_HIP_K_COSTVEC);
                 if (chunk_log)
@@ -2138,8 +2055,6 @@ int launch_parse(agc_hip_ctx *c, uint32_t n, uint8_t *out_bytes, uint32_t *out_u
                     total += sd.text.len;
                 fprintf(stderr, "    chunked launch mode %d: %u texts, %.2f Mb, longest %u, %u chunks of %u: chunk kernel %.3f ms, hop kernel %.3f ms\n", MODE, n, total / 1e6,
                         (uint32_t)b->segs[0].text.len, pl.n_jobs, chunk_len, a, b2);
-                for (auto &e : ev)
-                    (void)hipEventDestroy(e);
                 if (MODE != MODE_ESTIMATE) { // (the hop parser left its counters where an estimate's peak goes)
                     std::vector<uint32_t> dbg(n);
                     (void)hipMemcpy(dbg.data(), d_resp, (size_t)n * 4, hipMemcpyDeviceToHost);
@@ -2181,10 +2096,10 @@ int launch_parse(agc_hip_ctx *c, uint32_t n, uint8_t *out_bytes, uint32_t *out_u
         }
     }
     static const bool chunk_log2 = getenv("AGC_HIP_CHUNK_LOG") != nullptr;
-    hipEvent_t pe[2] = {nullptr, nullptr};
+    Event pe[2];
     if (chunk_log2 && b)
         for (auto &e : pe)
-            (void)hipEventCreate(&e);
+            (void)hipEventCreate(&e.h);
     {
         KTimer t(c, lane ? -1 : MODE == MODE_ENCODE ? AGC_HIP_K_ENCODE : MODE == MODE_ESTIMATE ? AGC_HIP_K_ESTIMATE : AGC_HIP_K_COSTVEC);
         if (pe[0])
@@ -2201,8 +2116,6 @@ int launch_parse(agc_hip_ctx *c, uint32_t n, uint8_t *out_bytes, uint32_t *out_u
         for (const SegDesc &sd : b->segs)
             total += sd.text.len;
         fprintf(stderr, "    whole-text launch mode %d: %u texts, %.2f Mb, longest %u: %.3f ms\n", MODE, n, total / 1e6, n ? (uint32_t)b->segs[0].text.len : 0u, a);
-        for (auto &e : pe)
-            (void)hipEventDestroy(e);
     }
     HIPCHK(c, hipGetLastError());
     return AGC_HIP_OK;
@@ -2275,14 +2188,7 @@ static int lz_encode_begin_impl(agc_hip_ctx *c, int lane, uint32_t n, const uint
     Batch b;
     CHK(prepare_batch(c, MODE_ENCODE, n, h_gid, src, h_off, h_len, h_rc, nullptr, b, lane));
     CHK(ensure(c, L.d_scratch, b.out_total + 64, L.s));
-    if (L.h_lens_cap < n) {
-        if (L.h_lens)
-            HIPCHK(c, hipHostFree(L.h_lens));
-        L.h_lens = nullptr;
-        L.h_lens_cap = 0;
-        HIPCHK(c, hipHostMalloc((void **)&L.h_lens, ((size_t)n + n / 4 + 1024) * 4, hipHostMallocDefault));
-        L.h_lens_cap = (size_t)n + n / 4 + 1024;
-    }
+    CHK(ensure_pinned(c, L.h_lens, (size_t)n * 4, ((size_t)n + n / 4 + 1024) * 4));
     L.timed = c->timing;
     if (L.timed)
         (void)hipEventRecord(L.e0, L.s);
@@ -2291,7 +2197,7 @@ static int lz_encode_begin_impl(agc_hip_ctx *c, int lane, uint32_t n, const uint
         (void)hipEventRecord(L.e1, L.s);
     HIPCHK(c, hipEventRecord(L.done, L.s));
     L.done_valid = true;
-    HIPCHK(c, hipMemcpyAsync(L.h_lens, L.d_resv.p, (size_t)n * 4, hipMemcpyDeviceToHost, L.s));
+    HIPCHK(c, hipMemcpyAsync(L.h_lens.p, L.d_resv.p, (size_t)n * 4, hipMemcpyDeviceToHost, L.s));
     L.pending = true;
     return AGC_HIP_OK;
 }
@@ -2545,7 +2451,7 @@ int agc_hip_lz_encode_end_on(agc_hip_ctx *c, uint32_t lane, uint8_t *h_enc, uint
     }
 #endif
     // (AGC_HIP_ECAP: still in flight -- call again with a larger buffer)
-    CHK(collect_deltas(c, {L.d_scratch, L.d_segs, L.d_resv, L.d_dstoff, L.d_compact}, L.s, n, L.h_lens, true, h_enc, enc_cap, h_enc_off, Laps("lz_encode_end", n)));
+    CHK(collect_deltas(c, {L.d_scratch, L.d_segs, L.d_resv, L.d_dstoff, L.d_compact}, L.s, n, L.h_lens.as<uint32_t>(), true, h_enc, enc_cap, h_enc_off, Laps("lz_encode_end", n)));
     L.pending = false;
     return AGC_HIP_OK;
 }
@@ -2583,7 +2489,7 @@ int agc_hip_host_alloc(agc_hip_ctx *c, uint64_t bytes, void **out)
     HIPCHK(c, hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault));
     {
         std::lock_guard<std::mutex> lk(c->host_alloc_mtx);
-        c->host_allocs.push_back(p);
+        c->host_allocs.emplace_back(p, (size_t)bytes);
     }
     *out = p;
     return AGC_HIP_OK;
@@ -2595,14 +2501,16 @@ int agc_hip_host_free(agc_hip_ctx *c, void *p)
         return AGC_HIP_EINVAL;
     if (!p)
         return AGC_HIP_OK;
+    PinnedBuf mine;
     {
         std::lock_guard<std::mutex> lk(c->host_alloc_mtx);
-        auto it = std::find(c->host_allocs.begin(), c->host_allocs.end(), p);
+        auto it = std::find_if(c->host_allocs.begin(), c->host_allocs.end(), [p](const PinnedBuf &b) { return b.p == p; });
         if (it == c->host_allocs.end())
             return AGC_HIP_EINVAL;
+        mine = std::move(*it);
         c->host_allocs.erase(it);
     }
-    if (hipHostFree(p) != hipSuccess) // (no write to the shared error string: this may be the thread that collects an encode)
+    if (mine.release() != hipSuccess) // (no write to the shared error string: this may be the thread that collects an encode)
         return AGC_HIP_ENODEV;
     return AGC_HIP_OK;
 }
@@ -2731,9 +2639,9 @@ int agc_hip_ref_store_begin_packed(agc_hip_ctx *c, uint32_t slot, uint32_t n_ref
     HIPCHK(c, hipSetDevice(c->device));
     agc_hip_ctx::RefStore &R = c->ref_store[slot];
     if (!c->ref_store_stream)
-        HIPCHK(c, hipStreamCreateWithFlags(&c->ref_store_stream, hipStreamNonBlocking));
+        HIPCHK(c, hipStreamCreateWithFlags(&c->ref_store_stream.h, hipStreamNonBlocking));
     if (!R.done)
-        HIPCHK(c, hipEventCreateWithFlags(&R.done, hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&R.done.h, hipEventDisableTiming));
     const hipStream_t st = c->ref_store_stream;
     if (R.pending) { // (a slot nobody collected: its copies must have landed before its buffers are written again)
         HIPCHK(c, hipEventSynchronize(R.done));
@@ -3135,16 +3043,8 @@ static int zstd17_batch_impl(agc_hip_ctx *c, uint32_t n, const uint8_t *h_src, c
         HIPCHK(c, hipGetLastError());
         done += m;
     }
-    if (c->h_zsizes_cap < n) {
-        if (c->h_zsizes)
-            HIPCHK(c, hipHostFree(c->h_zsizes));
-        c->h_zsizes = nullptr;
-        c->h_zsizes_cap = 0;
-        const size_t cap = (size_t)n + n / 4 + 1024;
-        HIPCHK(c, hipHostMalloc((void **)&c->h_zsizes, cap * 4, hipHostMallocDefault));
-        c->h_zsizes_cap = cap;
-    }
-    uint32_t *sizes = c->h_zsizes;
+    CHK(ensure_pinned(c, c->h_zsizes, (size_t)n * 4, ((size_t)n + n / 4 + 1024) * 4));
+    uint32_t *sizes = c->h_zsizes.as<uint32_t>();
     HIPCHK(c, hipMemcpyAsync(sizes, c->d_zsize.p, (size_t)n * 4, hipMemcpyDeviceToHost, zs_));
     // (the launch lasts hundreds of ms and the host pool compresses its share of the packs meanwhile: this thread sleeps)
     HIPCHK(c, hipEventRecord(c->zev_wait, zs_));

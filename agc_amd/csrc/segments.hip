@@ -49,22 +49,15 @@ int agc_hip_group_map_update(agc_hip_ctx *c, uint32_t n, const uint64_t *h_idx, 
     // context's stream); the buffer is reused once the event behind its last scatter has passed
     const size_t idx_bytes = ((size_t)n * 8 + 15) & ~(size_t)15, need = idx_bytes + (size_t)n * sizeof(GroupSlot);
     if (!c->gmap_ev)
-        HIPCHK(c, hipEventCreateWithFlags(&c->gmap_ev, hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&c->gmap_ev.h, hipEventDisableTiming));
     if (c->gmap_ev_valid)
         HIPCHK(c, hipEventSynchronize(c->gmap_ev));
-    if (c->h_gmap_stage_cap < need) {
-        if (c->h_gmap_stage)
-            HIPCHK(c, hipHostFree(c->h_gmap_stage));
-        c->h_gmap_stage = nullptr;
-        c->h_gmap_stage_cap = 0;
-        HIPCHK(c, hipHostMalloc(&c->h_gmap_stage, need + need / 2 + 4096, hipHostMallocDefault));
-        c->h_gmap_stage_cap = need + need / 2 + 4096;
-    }
+    CHK(ensure_pinned(c, c->h_gmap_stage, need, need + need / 2 + 4096));
     CHK(ensure(c, c->d_gmap_stage, need + 64));
-    memcpy(c->h_gmap_stage, h_idx, (size_t)n * 8);
-    memcpy((uint8_t *)c->h_gmap_stage + idx_bytes, h_slots, (size_t)n * sizeof(GroupSlot));
+    memcpy(c->h_gmap_stage.p, h_idx, (size_t)n * 8);
+    memcpy(c->h_gmap_stage.as<uint8_t>() + idx_bytes, h_slots, (size_t)n * sizeof(GroupSlot));
     uint8_t *st = (uint8_t *)c->d_gmap_stage.p;
-    HIPCHK(c, hipMemcpyAsync(st, c->h_gmap_stage, need, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(st, c->h_gmap_stage.p, need, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(gmap_scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, (GroupSlot *)c->d_gmap.p, (const uint64_t *)st,
                        (const GroupSlot *)(st + idx_bytes), n);
     HIPCHK(c, hipGetLastError());
@@ -102,19 +95,12 @@ static int launch_known(agc_hip_ctx *c)
     // a slot = len + 5 len / 16 + 64, rounded up to 16 (known_flag_kernel), and neighbouring segments share k <= 32 symbols:
     // per segment 32 * 21 / 16 + 64 + 15 < 128 bytes beyond its share of the sample
     const size_t scratch_ub = (size_t)(S.total + 5 * S.total / 16) + 128 * (size_t)n_ub + 64;
-    CHK(ensure(c, c->l2.d_segs, (size_t)n_ub * sizeof(SegDesc), c->stream2));
-    CHK(ensure(c, c->l2.d_resv, (size_t)n_ub * 4, c->stream2));
-    CHK(ensure(c, c->l2.d_resp, (size_t)n_ub * 4, c->stream2));
-    CHK(ensure(c, c->l2.d_scratch, scratch_ub, c->stream2));
-    CHK(ensure(c, c->l2.d_n, 64, c->stream2));
-    if (c->l2.h_lens_cap < n_ub) {
-        if (c->l2.h_lens)
-            HIPCHK(c, hipHostFree(c->l2.h_lens));
-        c->l2.h_lens = nullptr;
-        c->l2.h_lens_cap = 0;
-        HIPCHK(c, hipHostMalloc((void **)&c->l2.h_lens, ((size_t)n_ub + n_ub / 4 + 1024) * 4, hipHostMallocDefault));
-        c->l2.h_lens_cap = (size_t)n_ub + n_ub / 4 + 1024;
-    }
+    CHK(ensure(c, c->l2.d_segs, (size_t)n_ub * sizeof(SegDesc), c->l2.s));
+    CHK(ensure(c, c->l2.d_resv, (size_t)n_ub * 4, c->l2.s));
+    CHK(ensure(c, c->l2.d_resp, (size_t)n_ub * 4, c->l2.s));
+    CHK(ensure(c, c->l2.d_scratch, scratch_ub, c->l2.s));
+    CHK(ensure(c, c->l2.d_n, 64, c->l2.s));
+    CHK(ensure_pinned(c, c->l2.h_lens, (size_t)n_ub * 4, ((size_t)n_ub + n_ub / 4 + 1024) * 4));
     hipLaunchKernelGGL(known_flag_kernel, dim3((n_ub + 256) / 256), dim3(256), 0, st, segs, counts, (const RefDesc *)c->d_refs.p, (uint32_t)c->refs.size(), n_ub, flag,
                        capv);
     hipLaunchKernelGGL(scan_excl_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, flag, known_rank, n_ub + 1);
@@ -135,18 +121,18 @@ static int launch_known(agc_hip_ctx *c)
     HIPCHK(c, hipMemcpyAsync(d_n_known, &counts->n_known, 4, hipMemcpyDeviceToDevice, st));
     // the parse on the second lane, behind everything queued here
     HIPCHK(c, hipEventRecord(c->l2.ready, st));
-    HIPCHK(c, hipStreamWaitEvent(c->stream2, c->l2.ready, 0));
+    HIPCHK(c, hipStreamWaitEvent(c->l2.s, c->l2.ready, 0));
     c->l2.timed = c->timing;
     if (c->l2.timed)
-        (void)hipEventRecord(c->l2.e0, c->stream2);
+        (void)hipEventRecord(c->l2.e0, c->l2.s);
     CHK(launch_parse<MODE_ENCODE>(c, n_ub, (uint8_t *)c->l2.d_scratch.p, nullptr, 1, d_n_known));
     if (c->l2.timed)
-        (void)hipEventRecord(c->l2.e1, c->stream2);
-    HIPCHK(c, hipEventRecord(c->l2.done, c->stream2));
+        (void)hipEventRecord(c->l2.e1, c->l2.s);
+    HIPCHK(c, hipEventRecord(c->l2.done, c->l2.s));
     c->l2.done_valid = true;
-    HIPCHK(c, hipMemcpyAsync(c->l2.h_lens, c->l2.d_resv.p, (size_t)n_ub * 4, hipMemcpyDeviceToHost, c->stream2));
-    uint32_t *n_pinned = (uint32_t *)((uint8_t *)c->h_segcounts + 64);
-    HIPCHK(c, hipMemcpyAsync(n_pinned, d_n_known, 4, hipMemcpyDeviceToHost, c->stream2));
+    HIPCHK(c, hipMemcpyAsync(c->l2.h_lens.p, c->l2.d_resv.p, (size_t)n_ub * 4, hipMemcpyDeviceToHost, c->l2.s));
+    uint32_t *n_pinned = (uint32_t *)(c->h_segcounts.as<uint8_t>() + 64);
+    HIPCHK(c, hipMemcpyAsync(n_pinned, d_n_known, 4, hipMemcpyDeviceToHost, c->l2.s));
     c->l2.n_pinned = n_pinned;
     c->l2.n = 0;
     c->l2.pending = true;
@@ -174,35 +160,16 @@ int agc_hip_segments_packed(agc_hip_ctx *c, const agc_hip_packed *pk, const uint
         c->err = "segments_packed: the previous encode was not collected (agc_hip_lz_encode_end)";
         return AGC_HIP_EINVAL;
     }
-    static const bool laps = getenv("AGC_HIP_LAPS") != nullptr;
-    auto tnow = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double lt = laps ? tnow() : 0;
-    auto LAP = [&](const char *what) {
-        if (laps) {
-            const double t = tnow();
-            fprintf(stderr, "    segments_packed lap %s %.3f ms\n", what, t - lt);
-            lt = t;
-        }
-    };
+    Laps LAP("segments_packed", ~0u);
     // ---- raw hits: collected from the prefetch, or scanned now
     uint32_t n = 0;
     const ScanHit *d_hits = nullptr;
     agc_hip_ctx::Prefetch &pf = c->pf;
     bool from_pf = false;
     if (prefetched) {
-        if (!pf.valid || pf.words != pk->d_words || pf.n_symbols != pk->n_symbols || pf.k != k || pf.n_ctg != n_ctg || pf.first_off != h_ctg_off[0] ||
-            pf.last_off != h_ctg_off[n_ctg])
-            return AGC_HIP_EINVAL; // nothing, or something else, was prefetched
-        HIPCHK(c, hipStreamSynchronize(pf.stream));
-        if (pf.timed) {
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, pf.e0, pf.e1);
-            c->ms[AGC_HIP_K_SCAN] += ms;
-            c->launches[AGC_HIP_K_SCAN] += 1;
-            pf.timed = false;
-        }
-        if (pf.scanned && *pf.h_count <= pf.dev_cap) {
-            n = *pf.h_count;
+        CHK(collect_prefetch(c, pk, h_ctg_off, n_ctg, k));
+        if (pf.scanned && *pf.h_count.as<uint32_t>() <= pf.dev_cap) {
+            n = *pf.h_count.as<uint32_t>();
             d_hits = (const ScanHit *)pf.d_hits.p;
             from_pf = true;
         }
@@ -221,8 +188,7 @@ int agc_hip_segments_packed(agc_hip_ctx *c, const agc_hip_packed *pk, const uint
         *h_n_segs = n_ub;
         return AGC_HIP_ECAP; // (a prefetched scan stays valid: the second call collects it again)
     }
-    if (!c->h_segcounts)
-        HIPCHK(c, hipHostMalloc(&c->h_segcounts, 256, hipHostMallocDefault));
+    CHK(ensure_pinned(c, c->h_segcounts, 256, 256));
     // ---- work area
     auto layout = [&](uint8_t *p, bool assign) -> size_t {
         uint8_t *p0 = p;
@@ -328,12 +294,12 @@ int agc_hip_segments_packed(agc_hip_ctx *c, const agc_hip_packed *pk, const uint
         LAP("encode queued");
     }
     // ---- the segment table to the host (into pinned memory when the caller's buffer is: agc_hip_host_alloc)
-    HIPCHK(c, hipMemcpyAsync(c->h_segcounts, counts, sizeof(SegCounts), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(c->h_segcounts.p, counts, sizeof(SegCounts), hipMemcpyDeviceToHost, st));
     if (n_ub)
         HIPCHK(c, hipMemcpyAsync(h_segs, segs, (size_t)n_ub * sizeof(DevSeg), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     LAP("segments on the host");
-    const SegCounts hc = *(const SegCounts *)c->h_segcounts;
+    const SegCounts hc = *c->h_segcounts.as<const SegCounts>();
     *h_n_segs = hc.n_segs;
     if (launched) {
         // (the flags `encoded` were set before the copy: their number is the number of deltas; the device's own count arrives
@@ -344,7 +310,7 @@ int agc_hip_segments_packed(agc_hip_ctx *c, const agc_hip_packed *pk, const uint
         if (h_n_encoded)
             *h_n_encoded = ne;
         if (!ne) { // (no group was known: the launch had nothing to do and nothing is in flight)
-            HIPCHK(c, hipStreamSynchronize(c->stream2));
+            HIPCHK(c, hipStreamSynchronize(c->l2.s));
             c->l2.n_pinned = nullptr;
             c->l2.pending = false;
         }

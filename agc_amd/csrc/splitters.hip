@@ -129,28 +129,19 @@ extern "C" int agc_hip_determine_splitters_dev(agc_hip_ctx *c, const uint8_t *d_
     if (ranges.empty())
         return AGC_HIP_OK;
 
-    // buffers: keys/vals double-buffered for the sort, bitmap over absolute positions
+    // buffers: keys/vals double-buffered for the sort, bitmap over absolute positions (this call's own: they go when it returns)
     DevBuf keys0, keys1, vals0, vals1, tmp, bitmap;
-    auto release = [&]() {
-        for (DevBuf *b : {&keys0, &keys1, &vals0, &vals1, &tmp, &bitmap})
-            if (b->p)
-                (void)hipFree(b->p);
-    };
     int rc = AGC_HIP_OK;
-    auto fail = [&](int code) {
-        release();
-        return code;
-    };
     if ((rc = ensure(c, keys0, hi * 8)) || (rc = ensure(c, keys1, hi * 8)) || (rc = ensure(c, vals0, hi * 4)) ||
         (rc = ensure(c, vals1, hi * 4)) || (rc = ensure(c, bitmap, (hi / 32 + 2) * 4)))
-        return fail(rc);
+        return rc;
     if (hipMemsetAsync(keys0.p, 0xFF, hi * 8, c->stream) != hipSuccess || hipMemsetAsync(vals0.p, 0, hi * 4, c->stream) != hipSuccess ||
         hipMemsetAsync(bitmap.p, 0, (hi / 32 + 2) * 4, c->stream) != hipSuccess)
-        return fail(AGC_HIP_ENODEV);
+        return AGC_HIP_ENODEV;
     if ((rc = ensure(c, c->d_ranges, ranges.size() * sizeof(ScanRange))))
-        return fail(rc);
+        return rc;
     if ((rc = upload(c, c->d_ranges.p, ranges.data(), ranges.size() * sizeof(ScanRange), c->stream)))
-        return fail(rc);
+        return rc;
     {
         KTimer t(c, AGC_HIP_K_SCAN);
         hipLaunchKernelGGL(kmer_enum_kernel, dim3(grid_for((uint32_t)ranges.size(), 4, 4096)), dim3(256), 0, c->stream, d_codes,
@@ -161,23 +152,23 @@ extern "C" int agc_hip_determine_splitters_dev(agc_hip_ctx *c, const uint8_t *d_
     rocprim::double_buffer<uint32_t> dv((uint32_t *)vals0.p + lo, (uint32_t *)vals1.p + lo);
     size_t tmp_bytes = 0;
     if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, dk, dv, (size_t)total, 0, 64, c->stream) != hipSuccess)
-        return fail(AGC_HIP_ENODEV);
+        return AGC_HIP_ENODEV;
     if ((rc = ensure(c, tmp, tmp_bytes + 256)))
-        return fail(rc);
+        return rc;
     {
         KTimer t(c, AGC_HIP_K_INDEX);
         if (rocprim::radix_sort_pairs(tmp.p, tmp_bytes, dk, dv, (size_t)total, 0, 64, c->stream) != hipSuccess)
-            return fail(AGC_HIP_ENODEV);
+            return AGC_HIP_ENODEV;
     }
     const uint64_t *sk = dk.current();
     const uint32_t *sv = dv.current();
     hipLaunchKernelGGL(singleton_bitmap_kernel, dim3(4096), dim3(256), 0, c->stream, sk, sv, total, (uint32_t *)bitmap.p);
     if (hipGetLastError() != hipSuccess)
-        return fail(AGC_HIP_ENODEV);
+        return AGC_HIP_ENODEV;
     std::vector<uint32_t> bm(hi / 32 + 2);
     if (hipMemcpyAsync(bm.data(), bitmap.p, bm.size() * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess)
-        return fail(AGC_HIP_ENODEV);
+        return AGC_HIP_ENODEV;
 
     // adaptive mode keeps the sorted k-mers (singletons / duplicates are split by the caller)
     if (h_sorted_kmers && h_n_sorted) {
@@ -187,19 +178,17 @@ extern "C" int agc_hip_determine_splitters_dev(agc_hip_ctx *c, const uint8_t *d_
         while (a < b) {
             const uint64_t m = (a + b) / 2;
             if (hipMemcpy(probe.data(), sk + m, 8, hipMemcpyDeviceToHost) != hipSuccess)
-                return fail(AGC_HIP_ENODEV);
+                return AGC_HIP_ENODEV;
             if (probe[0] == ~0ULL)
                 b = m;
             else
                 a = m + 1;
         }
         *h_n_sorted = a;
-        if (a > sets_cap) {
-            release();
+        if (a > sets_cap)
             return AGC_HIP_ECAP;
-        }
         if (a && hipMemcpy(h_sorted_kmers, sk, a * 8, hipMemcpyDeviceToHost) != hipSuccess)
-            return fail(AGC_HIP_ENODEV);
+            return AGC_HIP_ENODEV;
     }
 
     // find_splitters_in_contig (agc_compressor.cpp:762-825) over the singleton bitmap
@@ -258,22 +247,16 @@ extern "C" int agc_hip_determine_splitters_dev(agc_hip_ctx *c, const uint8_t *d_
     std::vector<uint64_t> spl(spl_pos.size());
     if (!spl_pos.empty()) {
         DevBuf dpos, dout;
-        if ((rc = ensure(c, dpos, spl_pos.size() * 8)) || (rc = ensure(c, dout, spl_pos.size() * 8))) {
-            if (dpos.p)
-                (void)hipFree(dpos.p);
-            return fail(rc);
-        }
+        if ((rc = ensure(c, dpos, spl_pos.size() * 8)) || (rc = ensure(c, dout, spl_pos.size() * 8)))
+            return rc;
         rc = upload(c, dpos.p, spl_pos.data(), spl_pos.size() * 8, c->stream);
         hipLaunchKernelGGL(kmers_at_kernel, dim3((uint32_t)((spl_pos.size() + 255) / 256)), dim3(256), 0, c->stream, d_codes,
                            (const uint64_t *)dpos.p, (uint32_t)spl_pos.size(), k, (uint64_t *)dout.p);
         (void)hipMemcpyAsync(spl.data(), dout.p, spl.size() * 8, hipMemcpyDeviceToHost, c->stream);
         const hipError_t e2 = hipStreamSynchronize(c->stream);
-        (void)hipFree(dpos.p);
-        (void)hipFree(dout.p);
         if (rc || e2 != hipSuccess)
-            return fail(rc ? rc : AGC_HIP_ENODEV);
+            return rc ? rc : AGC_HIP_ENODEV;
     }
-    release();
     std::sort(spl.begin(), spl.end());
     spl.erase(std::unique(spl.begin(), spl.end()), spl.end());
     *h_n_splitters = spl.size();

@@ -370,6 +370,86 @@ def test_prefetched_scan_matches_oracle(hip_ctx, oracle, k):
         assert np.array_equal(back, oracle.rev_comp(codes[3:codes.size - 2])), i
 
 
+def _oracle_segments(oracle, contigs, k, spl):
+    want = []
+    for ci, c in enumerate(contigs):
+        s = oracle.scan_contig(c, k, spl)
+        for i in range(len(s["start"])):
+            want.append((ci, int(s["start"][i]), int(s["len"][i]), int(s["front_full"][i]), int(s["back_full"][i]),
+                         int(s["front_dir"][i]) if s["front_full"][i] else 0, int(s["back_dir"][i]) if s["back_full"][i] else 0))
+    return want
+
+
+def _segment_tuples(segs):
+    return [(int(g["ctg"]), int(g["start"]), int(g["len"]), int(g["front_full"]), int(g["back_full"]), int(g["front_dir"]), int(g["back_dir"])) for g in segs]
+
+
+@pytest.mark.parametrize("entry", ["scan_prefetched", "segments_packed"])
+def test_prefetched_scan_whose_hit_list_overflows(oracle, entry):
+    """Every k-mer of the contig is a splitter, so the raw hits (one per position, before the reset rule) outnumber the hit list of
+    a context that has scanned nothing yet: the prefetched list (total / 1000 + 4096 entries) overflows, whoever collects it scans
+    again the ordinary way, and that scan's first attempt (total / 2000 + 4096) overflows as well.  Both collectors must still
+    deliver what the oracle delivers."""
+    import ctypes as C
+    import torch
+    from agc_amd import capi
+    rng = np.random.default_rng(31)
+    k = 21
+    c = synth.random_seq(rng, 32 << 10)
+    allk = np.zeros(c.size, np.uint64)
+    n_raw = oracle.lib().agco_enumerate_kmers(c.ctypes.data_as(C.POINTER(C.c_uint8)), c.size, k, allk.ctypes.data_as(C.POINTER(C.c_uint64)))
+    assert n_raw > c.size // 1000 + 4096 >= c.size // 2000 + 4096  # (raw hits against the two floors)
+    spl = np.unique(allk[:n_raw])
+    off = np.array([0, c.size], np.uint64)
+    d = torch.from_numpy(c).cuda()
+    torch.cuda.synchronize()
+    ctx = capi.Context(0)  # (a fresh one: its hit lists are empty, both capacities are at their floor)
+    try:
+        pk, keep = ctx.pack_dev(d)
+        ctx.splitters_set(spl)
+        ctx.prefetch_packed_dev(pk, off, k)
+        if entry == "scan_prefetched":
+            got = ctx.scan_prefetched(pk, off, k)
+            want = _oracle_hits(oracle, [c], k, spl)
+            for g, w, name in zip(got, want, ("ctg", "pos", "dir", "rc")):
+                assert np.array_equal(g, w), name
+            assert np.all(np.diff(got[1].astype(np.int64)) == k)
+        else:
+            ctx.group_map_set({})
+            segs, _ = ctx.segments_packed(pk, off, k, prefetched=True, cap=8)
+            want = _oracle_segments(oracle, [c], k, spl)
+            assert _segment_tuples(segs) == want
+            assert len(want) > c.size // k - 2
+    finally:
+        ctx.close()
+
+
+def test_prefetch_of_another_sample_is_refused(hip_ctx):
+    """sample A is prefetched, sample B -- as long, other words -- is asked for: both collectors refuse with AGC_HIP_EINVAL"""
+    import ctypes as C
+    import torch
+    from agc_amd import capi
+    rng = np.random.default_rng(32)
+    k = 21
+    a, b = synth.random_seq(rng, 20_000), synth.random_seq(rng, 20_000)
+    off = np.array([0, a.size], np.uint64)
+    da, db = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
+    torch.cuda.synchronize()
+    pka, keep_a = hip_ctx.pack_dev(da)
+    pkb, keep_b = hip_ctx.pack_dev(db)
+    assert pka.n_symbols == pkb.n_symbols and pka.d_words != pkb.d_words
+    hip_ctx.splitters_set(np.array([1, 2, 3], np.uint64) << np.uint64(40))
+    hip_ctx.prefetch_packed_dev(pka, off, k)
+    n = C.c_uint64()
+    rc = hip_ctx.L.agc_hip_scan_prefetched(hip_ctx.h, C.byref(pkb), capi._p(off, capi.u64p), 1, k, 0, C.byref(n), None, None, None, None)
+    assert rc == capi.EINVAL
+    segs = np.zeros(64, capi.SEGMENT_DTYPE)
+    ne = C.c_uint32()
+    rc = hip_ctx.L.agc_hip_segments_packed(hip_ctx.h, C.byref(pkb), capi._p(off, capi.u64p), 1, k, 1, 0, segs.size, segs.ctypes.data, C.byref(n), C.byref(ne))
+    assert rc == capi.EINVAL
+    hip_ctx.scan_prefetched(pka, off, k)  # ... and A itself is still there to be collected
+
+
 def test_packed_scan_equals_byte_scan_on_a_big_sample(hip_ctx, oracle):
     """size-independent property at a larger size: the two scan kernels agree (50 Mbp, 6 contigs, a few escaped blocks)"""
     import torch
