@@ -421,6 +421,12 @@ class Context:
         self._chk(self.L.agc_hip_group_map_set(self.h, tab.ctypes.data, n))
         return tab
 
+    def group_map_upload(self, tab):
+        """a GROUP_SLOT_DTYPE array somebody else laid out, uploaded slot for slot as it is (group_map_set probes the keys in
+        itself): tables with chosen probe chains.  The caller answers for a free slot in every chain."""
+        tab = np.ascontiguousarray(tab, dtype=GROUP_SLOT_DTYPE)
+        self._chk(self.L.agc_hip_group_map_set(self.h, tab.ctypes.data, tab.size))
+
     def group_map_update(self, idx, slots):
         idx = _a(idx, np.uint64)
         slots = np.ascontiguousarray(slots, dtype=GROUP_SLOT_DTYPE)

@@ -290,6 +290,7 @@ int agc_hip_segments_packed(agc_hip_ctx *c, const agc_hip_packed *pk, const uint
     bool launched = false;
     if (encode_known && S.valid) {
         CHK(launch_known(c));
+        S.valid = false; // (these segments had their launch: agc_hip_segments_encode_known is for a call made without it)
         launched = true;
         LAP("encode queued");
     }

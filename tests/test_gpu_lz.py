@@ -183,12 +183,11 @@ def _split_point_oracle(oracle, ref1, ref2, mml, seg, rc1, pf1, rc2, pf2):
     return p, int(s[p])
 
 
-def test_split_point_matches_oracle(hip_ctx, oracle):
-    """agc_hip_lz_split_point_batch_dev against the oracle's two cost vectors + the reference's sums / arg-min, for every
-    orientation combination; segments = left part of one reference + right part of another (the destroyed-middle-splitter
-    shape), plus unrelated and tiny segments."""
-    import torch
-    from agc_amd import synth
+@pytest.fixture(scope="module")
+def split_cases(hip_ctx, oracle):
+    """segments = left part of one reference + right part of another (the destroyed-middle-splitter shape), plus unrelated and tiny
+    segments; the references registered (once) at gids 7000 and above; one job per segment and orientation combination with the
+    oracle's (pos, sum)"""
     rng = np.random.default_rng(4242)
     mml = 18
     k = 21
@@ -209,6 +208,24 @@ def test_split_point_matches_oracle(hip_ctx, oracle):
         segs.append(seg)
     for i, r in enumerate(refs):
         hip_ctx.ref_register(gid0 + i, r, mml)
+    g1, g2, si, r1, p1, r2, p2, want = [], [], [], [], [], [], [], []
+    for i, seg in enumerate(segs):
+        for combo in range(16):
+            rc1, pf1, rc2, pf2 = combo & 1, (combo >> 1) & 1, (combo >> 2) & 1, (combo >> 3) & 1
+            # the reference only uses (rc1 == !pf1) xor use_rc combinations, but the ABI takes any
+            g1.append(gid0 + 2 * i), g2.append(gid0 + 2 * i + 1), si.append(i)
+            r1.append(rc1), p1.append(pf1), r2.append(rc2), p2.append(pf2)
+            want.append(_split_point_oracle(oracle, refs[2 * i], refs[2 * i + 1], mml, seg, rc1, pf1, rc2, pf2))
+    return dict(segs=segs, g1=g1, g2=g2, seg_of_job=np.array(si), r1=r1, p1=p1, r2=r2, p2=p2, want=want)
+
+
+def test_split_point_matches_oracle(hip_ctx, oracle, split_cases):
+    """agc_hip_lz_split_point_batch_dev against the oracle's two cost vectors + the reference's sums / arg-min, for every
+    orientation combination; segments = left part of one reference + right part of another (the destroyed-middle-splitter
+    shape), plus unrelated and tiny segments."""
+    import torch
+    c = split_cases
+    segs = c["segs"]
     off = np.zeros(len(segs), np.uint64)
     ln = np.array([s.size for s in segs], np.uint32)
     off[1:] = np.cumsum(ln[:-1].astype(np.uint64) + 5)
@@ -216,16 +233,9 @@ def test_split_point_matches_oracle(hip_ctx, oracle):
     for o, s in zip(off, segs):
         buf[int(o):int(o) + s.size] = s
     d = torch.from_numpy(buf).cuda()
-    g1, g2, oo, ll, r1, p1, r2, p2, want = [], [], [], [], [], [], [], [], []
-    for i, seg in enumerate(segs):
-        for combo in range(16):
-            rc1, pf1, rc2, pf2 = combo & 1, (combo >> 1) & 1, (combo >> 2) & 1, (combo >> 3) & 1
-            # the reference only uses (rc1 == !pf1) xor use_rc combinations, but the ABI takes any
-            g1.append(gid0 + 2 * i), g2.append(gid0 + 2 * i + 1), oo.append(off[i]), ll.append(ln[i])
-            r1.append(rc1), p1.append(pf1), r2.append(rc2), p2.append(pf2)
-            want.append(_split_point_oracle(oracle, refs[2 * i], refs[2 * i + 1], mml, seg, rc1, pf1, rc2, pf2))
-    pos, sm = hip_ctx.lz_split_point_batch_dev(d.data_ptr(), g1, g2, oo, ll, r1, p1, r2, p2)
-    for j, (wp, ws) in enumerate(want):
+    oo, ll = off[c["seg_of_job"]], ln[c["seg_of_job"]]
+    pos, sm = hip_ctx.lz_split_point_batch_dev(d.data_ptr(), c["g1"], c["g2"], oo, ll, c["r1"], c["p1"], c["r2"], c["p2"])
+    for j, (wp, ws) in enumerate(c["want"]):
         assert (int(pos[j]), int(sm[j])) == (wp, ws), f"job {j} (segment {j // 16}, combo {j % 16}): got {(int(pos[j]), int(sm[j]))} want {(wp, ws)}"
 
 
@@ -235,12 +245,15 @@ def test_split_point_matches_oracle(hip_ctx, oracle):
 # gaps); here the texts lie in clean blocks, at every alignment inside the 16-symbol words, so that the 64-bit XOR compare,
 # the funnel shifts and the reversed reads of reverse-complemented texts are what runs.
 # ---------------------------------------------------------------------------------------------------------------------
-def _packed_sample(hip_ctx, texts, rng, gap_fill="acgt"):
-    """texts back to back with ragged gaps of random ACGT (clean blocks) or of N (escaped blocks) -> (Packed, keep, off, len, buf)"""
+def _packed_sample(hip_ctx, texts, rng, gap_fill="acgt", align=None):
+    """texts back to back with ragged gaps of random ACGT (clean blocks) or of N (escaped blocks) -> (Packed, keep, off, len, buf);
+    align: where in its 16-symbol word text i starts (the gap in front of it grows to that)"""
     import torch
     off, parts, o = [], [], 0
     for i, t in enumerate(texts):
         g = int(rng.integers(1, 40))
+        if align is not None:
+            g += (int(align[i]) - o - g) % 16
         parts.append(rng.integers(0, 4, g).astype(np.uint8) if gap_fill == "acgt" else np.full(g, 4, np.uint8))
         o += g
         off.append(o)
@@ -299,6 +312,24 @@ def test_packed_entry_points_match_oracle(hip_ctx, oracle, registered, gap_fill)
     for i, (_m, _r, text) in enumerate(registered):
         wc, wu = oracle.ref_lag_counts(text)
         assert np.array_equal(cnt[i], wc) and np.array_equal(cur[i], wu), i
+
+
+@pytest.mark.parametrize("gap_fill", ["acgt", "n"])
+def test_split_point_packed_matches_oracle(hip_ctx, oracle, split_cases, gap_fill):
+    """agc_hip_lz_split_point_batch_packed -- what the create path calls for a destroyed middle splitter -- on the segments of
+    test_split_point_matches_oracle inside a packed sample: in clean blocks, a segment at every alignment within a 16-symbol word
+    (the first four segments lie there twice), and between N gaps; every (pos, sum) of all 16 orientation combinations"""
+    c = split_cases
+    rng = np.random.default_rng(606)
+    place = list(range(len(c["segs"]))) + [0, 1, 2, 3]  # segment of every text of the sample
+    align = rng.permutation(16)
+    pk, keep, off, ln, buf = _packed_sample(hip_ctx, [c["segs"][i] for i in place], rng, gap_fill, align=align)
+    assert sorted(int(o) % 16 for o in off) == list(range(16))
+    for texts in (range(12), [12, 13, 14, 15] + list(range(4, 12))):  # the text each segment's jobs read
+        at = np.array(texts)[c["seg_of_job"]]
+        pos, sm = hip_ctx.lz_split_point_batch_packed(pk, c["g1"], c["g2"], off[at], ln[at], c["r1"], c["p1"], c["r2"], c["p2"])
+        for j, (wp, ws) in enumerate(c["want"]):
+            assert (int(pos[j]), int(sm[j])) == (wp, ws), f"job {j} (segment {j // 16}, combo {j % 16}, text {at[j]}): got {(int(pos[j]), int(sm[j]))} want {(wp, ws)}"
 
 
 def test_packed_references_out_of_a_sample(hip_ctx, oracle):
