@@ -15,7 +15,8 @@ LIB_PATH = os.path.join(HERE, "libagc_hip.so")
 OK, ENODEV, EINVAL, ENOMEM, ECAP, ENOREF = 0, -1, -2, -3, -4, -5
 K_SCAN, K_INDEX, K_ENCODE, K_ESTIMATE, K_COSTVEC, K_REVCOMP, K_PREPROCESS, K_REFSTORE = range(8)
 K_NAMES = ["scan", "index", "encode", "estimate", "costvec", "revcomp", "preprocess", "refstore", "zstd", "filter", "segments", "pack",
-           "decode_scan", "decode_write"]
+           "decode_scan", "decode_write", "fasta_out"]
+SEG_RAW, SEG_REF, SEG_DELTA = 0, 1, 2
 
 # every symbol include/agc_hip.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
@@ -30,6 +31,7 @@ SYMBOLS = [
     "agc_hip_lz_encode_batch_dev", "agc_hip_lz_encode_batch", "agc_hip_lz_encode_begin_dev", "agc_hip_lz_encode_end", "agc_hip_lz_encode_pending",
     "agc_hip_lz_encode_begin_packed_on", "agc_hip_lz_encode_end_on", "agc_hip_lz_encode_pending_on", "agc_hip_lz_encode_drop_on",
     "agc_hip_lz_decode_batch", "agc_hip_lz_decode_batch_dev",
+    "agc_hip_sample_fasta", "agc_hip_sample_fasta_dev",
     "agc_hip_host_alloc", "agc_hip_host_free",
     "agc_hip_lz_estimate_batch_dev", "agc_hip_lz_estimate_batch",
     "agc_hip_lz_cost_vector_batch_dev", "agc_hip_lz_cost_vector_batch",
@@ -67,6 +69,13 @@ class Segment(C.Structure):
                 ("store_rc", C.c_uint8), ("encoded", C.c_uint8)]
 
 
+class SegSrc(C.Structure):
+    """agc_hip_seg_src: where one segment of a contig comes from (SEG_RAW / SEG_REF / SEG_DELTA)"""
+    _fields_ = [("kind", C.c_uint32), ("gid", C.c_uint32), ("off", C.c_uint64), ("n_bytes", C.c_uint32), ("length", C.c_uint32),
+                ("rc", C.c_uint32), ("pad", C.c_uint32)]
+
+
+SEG_SRC_DTYPE = np.dtype([("kind", "<u4"), ("gid", "<u4"), ("off", "<u8"), ("n_bytes", "<u4"), ("length", "<u4"), ("rc", "<u4"), ("pad", "<u4")])
 SEGMENT_DTYPE = np.dtype([("start", "<u8"), ("front_dir", "<u8"), ("front_rc", "<u8"), ("back_dir", "<u8"), ("back_rc", "<u8"), ("ctg", "<u4"), ("len", "<u4"),
                           ("map_gid", "<i4"), ("front_full", "u1"), ("back_full", "u1"), ("store_rc", "u1"), ("encoded", "u1")])
 GROUP_SLOT_DTYPE = np.dtype([("k1", "<u8"), ("k2", "<u8"), ("gid", "<i4"), ("used", "<u4")])
@@ -129,6 +138,9 @@ def load():
     L.agc_hip_lz_encode_pending.argtypes = [vp, u32p]
     L.agc_hip_lz_decode_batch.argtypes = [vp, C.c_uint32, u32p, u8p, u64p, u8p, u8p, C.c_uint64, u64p]
     L.agc_hip_lz_decode_batch_dev.argtypes = [vp, C.c_uint32, u32p, u8p, u64p, u8p, vp, C.c_uint64, u64p]
+    fasta_head = [vp, C.c_uint32, u64p, C.POINTER(SegSrc), u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_char_p, u64p]
+    L.agc_hip_sample_fasta.argtypes = fasta_head + [vp, C.c_uint64, u64p]
+    L.agc_hip_sample_fasta_dev.argtypes = fasta_head + [vp, C.c_uint64, u64p]
     L.agc_hip_host_alloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
     L.agc_hip_host_free.argtypes = [vp, vp]
     L.agc_hip_lz_estimate_batch_dev.argtypes = [vp, C.c_uint32, u32p, vp, u64p, u32p, u8p, u32p, u32p]
@@ -636,6 +648,44 @@ class Context:
         ooff = np.zeros(g.size + 1, np.uint64)
         self._chk(self.L.agc_hip_lz_decode_batch_dev(self.h, g.size, _p(g, u32p), _p(e, u8p), _p(eo, u64p), _p(r, u8p), d_out, out_cap, _p(ooff, u64p)))
         return ooff
+
+    def _fasta_args(self, ctg_seg, segs, data, names, name_off):
+        cs, no = _a(ctg_seg, np.uint64), _a(name_off, np.uint64)
+        sg = np.ascontiguousarray(segs, dtype=SEG_SRC_DTYPE)
+        d = _a(data, np.uint8)
+        assert cs.size >= 1 and no.size == cs.size and (cs.size == 1 or int(cs[-1]) == sg.size)
+        return cs, sg, d, bytes(names), no
+
+    def sample_fasta_raw(self, fn, ctg_seg, segs, data, k, line_length, names, name_off, text_ptr, text_cap):
+        """the entry point itself (fn: agc_hip_sample_fasta or _dev) -> (return code, text length)"""
+        cs, sg, d, nm, no = self._fasta_args(ctg_seg, segs, data, names, name_off)
+        n = C.c_uint64(0)
+        rc_ = fn(self.h, cs.size - 1, _p(cs, u64p), sg.ctypes.data_as(C.POINTER(SegSrc)), _p(d, u8p), d.size, int(k), int(line_length), nm, _p(no, u64p),
+                 text_ptr, int(text_cap), C.byref(n))
+        return rc_, n.value
+
+    def sample_fasta(self, ctg_seg, segs, data, k, line_length, names, name_off, out=None):
+        """the FASTA text of a sample from its plan: contig c = segs[ctg_seg[c]:ctg_seg[c+1]] (SEG_SRC_DTYPE; RAW symbols and deltas in
+        `data`), its name names[name_off[c]:name_off[c+1]] -> the text (uint8).  out = (address, capacity): written there (e.g. pinned
+        memory of host_alloc) -> its length"""
+        if out is not None:
+            rc_, n = self.sample_fasta_raw(self.L.agc_hip_sample_fasta, ctg_seg, segs, data, k, line_length, names, name_off, out[0], out[1])
+            self._chk(rc_)
+            return n
+        rc_, n = self.sample_fasta_raw(self.L.agc_hip_sample_fasta, ctg_seg, segs, data, k, line_length, names, name_off, None, 0)
+        if rc_ != ECAP:  # (the first call sizes the text: nothing is launched)
+            self._chk(rc_)
+            return np.zeros(0, np.uint8)
+        text = np.empty(n, np.uint8)
+        rc_, n = self.sample_fasta_raw(self.L.agc_hip_sample_fasta, ctg_seg, segs, data, k, line_length, names, name_off, text.ctypes.data, text.size)
+        self._chk(rc_)
+        return text[:n]
+
+    def sample_fasta_dev(self, ctg_seg, segs, data, k, line_length, names, name_off, d_text, text_cap):
+        """the same, the text left at the device address d_text (text_cap bytes) -> its length"""
+        rc_, n = self.sample_fasta_raw(self.L.agc_hip_sample_fasta_dev, ctg_seg, segs, data, k, line_length, names, name_off, d_text, text_cap)
+        self._chk(rc_)
+        return n
 
     def lz_encode_batch(self, text, gids, off, length, rc=None, enc_cap=None):
         text = _a(text, np.uint8)

@@ -21,6 +21,7 @@
 #include "lz_kernels.hip"
 #include "seg_kernels.hip"
 #include "lz_decode_kernels.hip"
+#include "fasta_out_kernels.hip"
 #include "zstd_kernels.hip"
 
 using namespace agc;
@@ -155,6 +156,7 @@ struct agc_hip_ctx {
     DevBuf d_ranges, d_hits, d_counter, d_segs, d_slices, d_scratch, d_resv, d_resp, d_dstoff, d_compact,
         d_jobs, d_counts, d_in, d_pp_cnt, d_pp_off, d_pp_total, d_lag, d_sample, d_zsrc, d_zdst, d_zws, d_zjobs, d_zsize, d_zout, d_zdstoff, d_maybe, d_fjobs;
     DevBuf d_dec_enc, d_dec_jobs, d_dec_res, d_dec_out; // agc_hip_lz_decode_batch*: the deltas, their descriptors, lengths + status, the symbols
+    DevBuf d_fa_sym, d_fa_copy, d_fa_plan, d_fa_text;   // agc_hip_sample_fasta*: the sample's symbols, the copy jobs, the text plan, the text
 
     PackTemp pk1;        // byte-input entry points on the first stream
     PackTemp pk_sample;  // agc_hip_sample_pack
@@ -2302,6 +2304,168 @@ static int lz_decode_impl(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, con
     return AGC_HIP_OK;
 }
 
+// The FASTA text of a sample (include/agc_hip.h) on the first stream.  The layout -- and with it the text's size -- follows from the
+// plan alone; then every segment is checked (the deltas by lz_decode_scan_kernel, against the length the plan declares) before
+// anything is written: lz_decode_write_kernel and segment_copy_kernel lay the segments out in the symbol buffer, fasta_text_kernel
+// writes the text.  d_text: the caller's device buffer, or nullptr: the context's, copied to h_text.
+static int sample_fasta_impl(agc_hip_ctx *c, uint32_t n_ctg, const uint64_t *h_ctg_seg, const agc_hip_seg_src *h_seg, const uint8_t *h_bytes, uint64_t n_bytes,
+                             uint32_t k, uint32_t line_length, const char *h_names, const uint64_t *h_name_off, uint8_t *h_text, uint8_t *d_text,
+                             uint64_t text_cap, uint64_t *h_text_len)
+{
+    *h_text_len = 0;
+    if (!n_ctg)
+        return AGC_HIP_OK;
+    const uint64_t n_seg = h_ctg_seg[n_ctg];
+    bool ascending = h_ctg_seg[0] == 0 && n_seg <= 0xFFFFFFFFull;
+    for (uint32_t ci = 0; ci < n_ctg; ++ci)
+        ascending = ascending && h_ctg_seg[ci] <= h_ctg_seg[ci + 1] && h_ctg_seg[ci + 1] <= n_seg && h_name_off[ci] <= h_name_off[ci + 1];
+    if (!ascending) {
+        c->err = "sample_fasta: the contigs' segment ranges or name offsets do not ascend from 0";
+        return AGC_HIP_EINVAL;
+    }
+    std::vector<uint64_t> ctg_text(n_ctg + 1), ctg_sym(n_ctg), seg_start(n_seg), seg_off(n_seg);
+    std::vector<uint32_t> skip(n_seg);
+    std::vector<DecodeJob> dj;
+    std::vector<uint32_t> dj_seg;
+    std::vector<CopyJob> cj;
+    int bad = AGC_HIP_OK; // the first complaint; reported once the text's size is known
+    uint64_t sym_total = 0, text = 0;
+    for (uint32_t ci = 0; ci < n_ctg; ++ci) {
+        uint64_t pos = 0;
+        for (uint64_t s = h_ctg_seg[ci]; s < h_ctg_seg[ci + 1]; ++s) {
+            const agc_hip_seg_src &g = h_seg[s];
+            const uint32_t sk = s == h_ctg_seg[ci] ? 0 : k;
+            const char *why = nullptr;
+            int code = AGC_HIP_EINVAL;
+            if (g.kind > AGC_HIP_SEG_DELTA)
+                why = "has an unknown kind";
+            else if (g.kind != AGC_HIP_SEG_REF && (g.off > n_bytes || g.n_bytes > n_bytes - g.off))
+                why = "names bytes outside the byte buffer";
+            else if (g.kind == AGC_HIP_SEG_RAW && g.n_bytes != g.length)
+                why = "is raw and its byte count differs from its length";
+            else if (g.kind != AGC_HIP_SEG_RAW && (g.gid >= c->refs.size() || !c->refs[g.gid].valid))
+                why = "names a group without a registered reference", code = AGC_HIP_ENOREF;
+            else if (g.kind == AGC_HIP_SEG_REF && c->refs[g.gid].ref_size != g.length)
+                why = "is a reference whose size differs from its length";
+            else if (g.length < sk)
+                why = "is shorter than the overlap with the segment in front of it";
+            if (why && bad == AGC_HIP_OK) {
+                c->err = "sample_fasta: segment " + std::to_string(s) + " (contig " + std::to_string(ci) + ") " + why;
+                bad = code;
+            }
+            seg_start[s] = pos;
+            seg_off[s] = sym_total;
+            skip[s] = sk;
+            if (!why && g.kind == AGC_HIP_SEG_DELTA) {
+                dj.push_back({g.off, g.n_bytes, sym_total, g.length, g.gid, g.rc ? 1u : 0u, 0});
+                dj_seg.push_back((uint32_t)s);
+            } else if (!why && g.length)
+                cj.push_back({g.off, sym_total, g.length, g.gid, g.rc ? 1u : 0u, g.kind == AGC_HIP_SEG_REF ? 1u : 0u});
+            pos += g.length >= sk ? g.length - sk : 0;
+            sym_total += g.length;
+        }
+        ctg_sym[ci] = pos;
+        ctg_text[ci] = text;
+        text += fo::contig_text_bytes(h_name_off[ci + 1] - h_name_off[ci], pos, line_length);
+    }
+    ctg_text[n_ctg] = text;
+    *h_text_len = text;
+    if (bad != AGC_HIP_OK)
+        return bad;
+    if (text > text_cap) {
+        c->err = "sample_fasta: the text buffer holds " + std::to_string(text_cap) + " bytes, " + std::to_string(text) + " are needed";
+        return AGC_HIP_ECAP;
+    }
+    const uint32_t a = d_text ? (uint32_t)((uintptr_t)d_text & (fo::CHUNK - 1)) : 0;
+    const uint64_t n_chunks = fo::chunk_count(a, text), text_blocks = (n_chunks + 255) / 256;
+    if (text_blocks > 0x7FFFFFFFull) {
+        c->err = "sample_fasta: a text of " + std::to_string(text) + " bytes is more than one launch writes";
+        return AGC_HIP_EINVAL;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(upload_refs(c));
+    CHK(ensure(c, c->d_dec_enc, n_bytes + 64));
+    if (n_bytes)
+        CHK(upload(c, c->d_dec_enc.p, h_bytes, n_bytes, c->stream));
+    const dim3 block(4 * WAVE); // a wave per segment
+    const uint32_t n_dj = (uint32_t)dj.size(), n_cj = (uint32_t)cj.size();
+    if (n_dj) {
+        CHK(ensure(c, c->d_dec_jobs, (size_t)n_dj * sizeof(DecodeJob)));
+        CHK(ensure(c, c->d_dec_res, (size_t)n_dj * sizeof(DecodeResult)));
+        CHK(upload(c, c->d_dec_jobs.p, dj.data(), (size_t)n_dj * sizeof(DecodeJob), c->stream));
+        {
+            KTimer t(c, AGC_HIP_K_DECODE_SCAN);
+            hipLaunchKernelGGL(lz_decode_scan_kernel, dim3((n_dj + 3) / 4), block, 0, c->stream, (const RefDesc *)c->d_refs.p, (const DecodeJob *)c->d_dec_jobs.p, n_dj,
+                               (const uint8_t *)c->d_dec_enc.p, (DecodeResult *)c->d_dec_res.p);
+        }
+        HIPCHK(c, hipGetLastError());
+        std::vector<DecodeResult> res(n_dj);
+        HIPCHK(c, hipMemcpyAsync(res.data(), c->d_dec_res.p, (size_t)n_dj * sizeof(DecodeResult), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (uint32_t i = 0; i < n_dj; ++i)
+            if (res[i].status != lzd::OK || res[i].len != dj[i].out_len) {
+                c->err = "sample_fasta: segment " + std::to_string(dj_seg[i]) +
+                         (res[i].status != lzd::OK ? " has a malformed delta" : " decodes to " + std::to_string(res[i].len) + " symbols, its length says " + std::to_string(dj[i].out_len));
+                return AGC_HIP_EINVAL;
+            }
+    }
+    // every segment has passed: from here on things are written
+    CHK(ensure(c, c->d_fa_sym, sym_total + 64));
+    uint8_t *d_sym = c->d_fa_sym.as<uint8_t>();
+    if (n_dj) {
+        KTimer t(c, AGC_HIP_K_DECODE_WRITE);
+        hipLaunchKernelGGL(lz_decode_write_kernel, dim3((n_dj + 3) / 4), block, 0, c->stream, (const RefDesc *)c->d_refs.p, (const DecodeJob *)c->d_dec_jobs.p, n_dj,
+                           (const uint8_t *)c->d_dec_enc.p, d_sym);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (n_cj) {
+        CHK(ensure(c, c->d_fa_copy, (size_t)n_cj * sizeof(CopyJob)));
+        CHK(upload(c, c->d_fa_copy.p, cj.data(), (size_t)n_cj * sizeof(CopyJob), c->stream));
+        KTimer t(c, AGC_HIP_K_FASTA_OUT);
+        hipLaunchKernelGGL(segment_copy_kernel, dim3((n_cj + 3) / 4), block, 0, c->stream, (const RefDesc *)c->d_refs.p, (const CopyJob *)c->d_fa_copy.p, n_cj,
+                           (const uint8_t *)c->d_dec_enc.p, d_sym);
+    }
+    HIPCHK(c, hipGetLastError());
+    // the plan in one upload: the 64-bit arrays, the 32-bit one, the names
+    const uint64_t names0 = h_name_off[0], names_bytes = h_name_off[n_ctg] - names0;
+    const size_t o_ctg_text = 0, o_ctg_seg = o_ctg_text + 8 * ((size_t)n_ctg + 1), o_ctg_sym = o_ctg_seg + 8 * ((size_t)n_ctg + 1), o_name_off = o_ctg_sym + 8 * (size_t)n_ctg,
+                 o_seg_start = o_name_off + 8 * ((size_t)n_ctg + 1), o_seg_off = o_seg_start + 8 * n_seg, o_skip = o_seg_off + 8 * n_seg, o_names = o_skip + 4 * n_seg,
+                 plan_bytes = o_names + names_bytes;
+    std::vector<uint8_t> plan(plan_bytes);
+    std::vector<uint64_t> name_off(h_name_off, h_name_off + n_ctg + 1);
+    for (uint64_t &o : name_off)
+        o -= names0;
+    std::memcpy(plan.data() + o_ctg_text, ctg_text.data(), 8 * ((size_t)n_ctg + 1));
+    std::memcpy(plan.data() + o_ctg_seg, h_ctg_seg, 8 * ((size_t)n_ctg + 1));
+    std::memcpy(plan.data() + o_ctg_sym, ctg_sym.data(), 8 * (size_t)n_ctg);
+    std::memcpy(plan.data() + o_name_off, name_off.data(), 8 * ((size_t)n_ctg + 1));
+    if (n_seg) {
+        std::memcpy(plan.data() + o_seg_start, seg_start.data(), 8 * n_seg);
+        std::memcpy(plan.data() + o_seg_off, seg_off.data(), 8 * n_seg);
+        std::memcpy(plan.data() + o_skip, skip.data(), 4 * n_seg);
+    }
+    if (names_bytes)
+        std::memcpy(plan.data() + o_names, h_names + names0, names_bytes);
+    CHK(ensure(c, c->d_fa_plan, plan_bytes + 64));
+    CHK(upload(c, c->d_fa_plan.p, plan.data(), plan_bytes, c->stream));
+    if (!d_text) {
+        CHK(ensure(c, c->d_fa_text, text + 64));
+        d_text = c->d_fa_text.as<uint8_t>();
+    }
+    const uint8_t *pl = c->d_fa_plan.as<uint8_t>();
+    const TextPlan P = {(g_u64 *)(pl + o_ctg_text), (g_u64 *)(pl + o_ctg_seg), (g_u64 *)(pl + o_ctg_sym), (g_u64 *)(pl + o_name_off), (g_u8 *)(pl + o_names),
+                        (g_u64 *)(pl + o_seg_start), (g_u64 *)(pl + o_seg_off), (g_u32 *)(pl + o_skip), (g_u8 *)d_sym, n_ctg, line_length};
+    {
+        KTimer t(c, AGC_HIP_K_FASTA_OUT);
+        hipLaunchKernelGGL(fasta_text_kernel, dim3((uint32_t)text_blocks), dim3(256), 0, c->stream, P, d_text, a, text, n_chunks);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (h_text)
+        HIPCHK(c, hipMemcpyAsync(h_text, d_text, text, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return AGC_HIP_OK;
+}
+
 extern "C" {
 
 int agc_hip_lz_encode_batch_packed(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const agc_hip_packed *pk, const uint64_t *h_off,
@@ -2476,6 +2640,22 @@ int agc_hip_lz_decode_batch_dev(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gi
     if (!n)
         return AGC_HIP_OK;
     return lz_decode_impl(c, n, h_gid, h_enc, h_enc_off, h_rc, nullptr, d_out, out_cap, h_out_off);
+}
+
+int agc_hip_sample_fasta(agc_hip_ctx *c, uint32_t n_ctg, const uint64_t *h_ctg_seg, const agc_hip_seg_src *h_seg, const uint8_t *h_bytes, uint64_t n_bytes, uint32_t k,
+                         uint32_t line_length, const char *h_names, const uint64_t *h_name_off, uint8_t *h_text, uint64_t text_cap, uint64_t *h_text_len)
+{
+    if (!c || !h_text_len || (n_ctg && (!h_ctg_seg || !h_name_off || (h_ctg_seg[n_ctg] && !h_seg) || (n_bytes && !h_bytes))) || (text_cap && !h_text))
+        return AGC_HIP_EINVAL;
+    return sample_fasta_impl(c, n_ctg, h_ctg_seg, h_seg, h_bytes, n_bytes, k, line_length, h_names, h_name_off, h_text, nullptr, text_cap, h_text_len);
+}
+
+int agc_hip_sample_fasta_dev(agc_hip_ctx *c, uint32_t n_ctg, const uint64_t *h_ctg_seg, const agc_hip_seg_src *h_seg, const uint8_t *h_bytes, uint64_t n_bytes, uint32_t k,
+                             uint32_t line_length, const char *h_names, const uint64_t *h_name_off, uint8_t *d_text, uint64_t text_cap, uint64_t *h_text_len)
+{
+    if (!c || !h_text_len || (n_ctg && (!h_ctg_seg || !h_name_off || (h_ctg_seg[n_ctg] && !h_seg) || (n_bytes && !h_bytes))) || (text_cap && !d_text))
+        return AGC_HIP_EINVAL;
+    return sample_fasta_impl(c, n_ctg, h_ctg_seg, h_seg, h_bytes, n_bytes, k, line_length, h_names, h_name_off, nullptr, d_text, text_cap, h_text_len);
 }
 
 // pinned host memory for the buffers results are copied into (a copy into pageable memory goes through a bounce buffer)

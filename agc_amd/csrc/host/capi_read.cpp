@@ -11,6 +11,10 @@ struct agc_t {
     agc::CAGCFile f;
 };
 
+struct agc_plan_t {
+    agc::SamplePlan p;
+};
+
 static char **vec2list(const std::vector<std::string> &v)
 {
     char **list = (char **)malloc(sizeof(char *) * (v.size() + 1));
@@ -155,6 +159,50 @@ int agc_get_params(const agc_t *agc, unsigned *k, unsigned *mml, unsigned *pack,
     *mml = b;
     *pack = c;
     *segment_size = d;
+    return 0;
+}
+
+agc_plan_t *agc_get_sample_plan(const agc_t *agc, const char *sample)
+{
+    if (!agc || !sample)
+        return nullptr;
+    agc_plan_t *pl = new agc_plan_t;
+    if (!agc->f.GetSamplePlan(sample, pl->p)) {
+        delete pl;
+        return nullptr;
+    }
+    return pl;
+}
+
+int agc_plan_fields(const agc_plan_t *plan, agc_plan_view *out)
+{
+    if (!plan || !out)
+        return -1;
+    const agc::SamplePlan &p = plan->p;
+    out->n_ctg = p.ctg_seg.size() - 1;
+    out->n_seg = p.kind.size();
+    out->n_bytes = p.bytes.size();
+    out->n_groups = p.groups.size();
+    out->names = (const char *)p.names.data();
+    out->name_off = p.name_off.data();
+    out->ctg_seg = p.ctg_seg.data();
+    out->group_id = p.group_id.data();
+    out->in_group_id = p.in_group_id.data();
+    out->rc = p.rc.data();
+    out->length = p.length.data();
+    out->kind = p.kind.data();
+    out->seg_bytes = p.n_bytes.data();
+    out->off = p.off.data();
+    out->bytes = p.bytes.data();
+    out->groups = p.groups.data();
+    out->ref_off = p.ref_off.data();
+    out->ref_bytes = p.ref_bytes.data();
+    return 0;
+}
+
+int agc_plan_destroy(agc_plan_t *plan)
+{
+    delete plan;
     return 0;
 }
 }

@@ -527,6 +527,68 @@ bool CAGCFile::GetSampleCodes(const std::string &sample, std::vector<std::string
     return true;
 }
 
+// The sources of decode_contig's segments instead of the segments: get_segment's three cases without its decode
+bool CAGCFile::GetSamplePlan(const std::string &sample, SamplePlan &P) const
+{
+    if (!p->opened)
+        return false;
+    auto it = p->sample_ids.find(sample);
+    if (it == p->sample_ids.end() || !p->ensure_sample(it->second))
+        return false;
+    const SampleDesc &sd = p->samples[it->second];
+    P = SamplePlan();
+    p->warm_refs(sd);
+    P.name_off.push_back(0);
+    P.ctg_seg.push_back(0);
+    for (const CtgDesc &c : sd.ctgs) {
+        P.names.insert(P.names.end(), c.name.begin(), c.name.end());
+        P.name_off.push_back(P.names.size());
+        for (const SegDesc &s : c.segs) {
+            const bool raw = s.group_id < NO_RAW_GROUPS;
+            uint32_t kind = raw ? SamplePlan::RAW : s.in_group_id == 0 ? SamplePlan::REF : SamplePlan::DELTA, length = s.raw_length;
+            uint64_t off = 0;
+            size_t n = 0;
+            if (kind == SamplePlan::REF) {
+                const bytes_t *ref;
+                if (!p->get_ref(s.group_id, ref))
+                    return false;
+                length = (uint32_t)ref->size();
+            } else {
+                const uint32_t idx = raw ? s.in_group_id : s.in_group_id - 1;
+                const bytes_t *pk;
+                const uint8_t *b;
+                if (!p->get_pack(s.group_id, idx / p->pack, pk) || !nth_in_pack(*pk, idx % p->pack, b, n) || n > 0xFFFFFFFFull)
+                    return false;
+                off = P.bytes.size();
+                P.bytes.insert(P.bytes.end(), b, b + n);
+                if (raw)
+                    length = (uint32_t)n;
+            }
+            if (!raw)
+                P.groups.push_back(s.group_id);
+            P.group_id.push_back(s.group_id);
+            P.in_group_id.push_back(s.in_group_id);
+            P.rc.push_back(s.rc ? 1 : 0);
+            P.length.push_back(length);
+            P.kind.push_back(kind);
+            P.n_bytes.push_back((uint32_t)n);
+            P.off.push_back(off);
+        }
+        P.ctg_seg.push_back(P.kind.size());
+    }
+    std::sort(P.groups.begin(), P.groups.end());
+    P.groups.erase(std::unique(P.groups.begin(), P.groups.end()), P.groups.end());
+    P.ref_off.push_back(0);
+    for (uint32_t g : P.groups) {
+        const bytes_t *ref;
+        if (!p->get_ref(g, ref))
+            return false;
+        P.ref_bytes.insert(P.ref_bytes.end(), ref->begin(), ref->end());
+        P.ref_off.push_back(P.ref_bytes.size());
+    }
+    return true;
+}
+
 bool CAGCFile::GetSampleFasta(const std::string &sample, std::string &out, uint32_t line_length) const
 {
     if (!p->opened)

@@ -12,6 +12,23 @@
 
 namespace agc {
 
+// What a device needs to write a sample's FASTA text without this reader's decode loop (GetSamplePlan): the contigs in archive
+// order, every segment's source and length, the bytes the sources name cut out of the decoded packs, and the references of the
+// groups the sample touches.  Everything behind zstd is left to the caller.
+struct SamplePlan {
+    enum Kind : uint32_t { RAW = 0, REF = 1, DELTA = 2 }; // a raw group's symbols; a group's reference as it is; a delta against it
+    std::vector<uint8_t> names;     // the contig names back to back
+    std::vector<uint64_t> name_off; // n_ctg + 1
+    std::vector<uint64_t> ctg_seg;  // n_ctg + 1: contig c = segments [ctg_seg[c], ctg_seg[c + 1])
+    // per segment (length: its symbols as decode_contig gets them, the overlap included; off / n_bytes: RAW, DELTA -- its bytes in `bytes`)
+    std::vector<uint32_t> group_id, in_group_id, rc, length, kind, n_bytes;
+    std::vector<uint64_t> off;
+    std::vector<uint8_t> bytes;     // every DELTA's delta, every RAW's symbols
+    std::vector<uint32_t> groups;   // the distinct groups >= 16 the sample needs, ascending
+    std::vector<uint64_t> ref_off;  // groups.size() + 1: group i's reference symbols = ref_bytes[ref_off[i], ref_off[i + 1])
+    std::vector<uint8_t> ref_bytes;
+};
+
 class CAGCFile {
     struct Impl;
     std::unique_ptr<Impl> p;
@@ -41,6 +58,8 @@ public:
     bool GetSampleCodes(const std::string &sample, std::vector<std::string> &names, std::vector<std::vector<uint8_t>> &codes) const;
     // the same, written contig by contig to an open stream (what the CLI uses: no sample-size string is built)
     bool WriteSampleFasta(const std::string &sample, FILE *f, uint32_t line_length = 80) const;
+    // the plan of a whole sample (see SamplePlan); false: unknown sample or an unreadable part
+    bool GetSamplePlan(const std::string &sample, SamplePlan &plan) const;
     // one `agc getctg` query -- contig[@sample][:from-to] (agc_decompressor_lib.h:127-130) -- as FASTA text;
     // the header is the full contig name (+ ":from-to" when a range was given), core/agc_decompressor.cpp:478-567
     bool GetContigFasta(const std::string &query, std::string &out, uint32_t line_length, std::string &err) const;

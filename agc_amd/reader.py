@@ -10,7 +10,18 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libagc_read.so")
 SYMBOLS = ["agc_open", "agc_close", "agc_get_ctg_len", "agc_get_ctg_seq", "agc_n_sample", "agc_n_ctg", "agc_reference_sample",
-           "agc_list_sample", "agc_list_ctg", "agc_list_destroy", "agc_string_destroy", "agc_get_sample_fasta", "agc_get_params"]
+           "agc_list_sample", "agc_list_ctg", "agc_list_destroy", "agc_string_destroy", "agc_get_sample_fasta", "agc_get_params",
+           "agc_get_sample_plan", "agc_plan_fields", "agc_plan_destroy"]
+PLAN_RAW, PLAN_REF, PLAN_DELTA = 0, 1, 2
+
+
+class PlanView(C.Structure):
+    """agc_plan_view (include/agc_read.h)"""
+    _u32p, _u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+    _fields_ = [("n_ctg", C.c_uint64), ("n_seg", C.c_uint64), ("n_bytes", C.c_uint64), ("n_groups", C.c_uint64),
+                ("names", C.c_void_p), ("name_off", _u64p), ("ctg_seg", _u64p),
+                ("group_id", _u32p), ("in_group_id", _u32p), ("rc", _u32p), ("length", _u32p), ("kind", _u32p), ("seg_bytes", _u32p),
+                ("off", _u64p), ("bytes", C.c_void_p), ("groups", _u32p), ("ref_off", _u64p), ("ref_bytes", C.c_void_p)]
 
 _lib = None
 
@@ -41,6 +52,10 @@ def load():
     L.agc_get_sample_fasta.restype = vp
     L.agc_get_sample_fasta.argtypes = [vp, cp, ci, C.POINTER(C.c_longlong)]
     L.agc_get_params.argtypes = [vp] + [C.POINTER(C.c_uint)] * 4
+    L.agc_get_sample_plan.restype = vp
+    L.agc_get_sample_plan.argtypes = [vp, cp]
+    L.agc_plan_fields.argtypes = [vp, C.POINTER(PlanView)]
+    L.agc_plan_destroy.argtypes = [vp]
     _lib = L
     return L
 
@@ -144,3 +159,36 @@ class CAGCFile:
         if self.L.agc_get_params(self.h, *[C.byref(x) for x in v]) != 0:
             return None
         return dict(zip(("k", "min_match_len", "pack_cardinality", "segment_size"), (x.value for x in v)))
+
+    def GetSamplePlan(self, sample):
+        """the plan of a whole sample (agc_get_sample_plan) as numpy arrays of their own, or None for an unknown sample:
+        names (bytes) / name_off, ctg_seg, per segment group_id / in_group_id / rc / length / kind (PLAN_*) / seg_bytes / off, the
+        byte blob `bytes` the RAW and DELTA segments name, groups (>= 16, ascending) with ref_off / ref_bytes"""
+        import numpy as np
+        h = self.L.agc_get_sample_plan(self.h, sample.encode()) if self.h else None
+        if not h:
+            return None
+        try:
+            v = PlanView()
+            if self.L.agc_plan_fields(h, C.byref(v)) != 0:
+                return None
+
+            def arr(ptr, n, dt):
+                n = int(n)
+                if not n:
+                    return np.zeros(0, dt)
+                addr = ptr if isinstance(ptr, int) else C.addressof(ptr.contents)
+                return np.frombuffer((C.c_char * (n * np.dtype(dt).itemsize)).from_address(addr), dtype=dt).copy()
+
+            out = {"name_off": arr(v.name_off, v.n_ctg + 1, np.uint64), "ctg_seg": arr(v.ctg_seg, v.n_ctg + 1, np.uint64)}
+            out["names"] = arr(v.names, out["name_off"][-1], np.uint8).tobytes()
+            for f in ("group_id", "in_group_id", "rc", "length", "kind", "seg_bytes"):
+                out[f] = arr(getattr(v, f), v.n_seg, np.uint32)
+            out["off"] = arr(v.off, v.n_seg, np.uint64)
+            out["bytes"] = arr(v.bytes, v.n_bytes, np.uint8)
+            out["groups"] = arr(v.groups, v.n_groups, np.uint32)
+            out["ref_off"] = arr(v.ref_off, v.n_groups + 1, np.uint64)
+            out["ref_bytes"] = arr(v.ref_bytes, out["ref_off"][-1], np.uint8)
+            return out
+        finally:
+            self.L.agc_plan_destroy(h)

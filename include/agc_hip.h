@@ -62,7 +62,8 @@ enum {
     AGC_HIP_K_PACK = 11,     /* agc_hip_pack_fasta_*: raw FASTA bodies -> the 2-bit packed sample in one pass (pack_kernels.hip) */
     AGC_HIP_K_DECODE_SCAN = 12,  /* lz_decode_scan_kernel: length and status of every delta (lz_decode_kernels.hip) */
     AGC_HIP_K_DECODE_WRITE = 13, /* lz_decode_write_kernel: the decoded symbols */
-    AGC_HIP_K_COUNT = 14
+    AGC_HIP_K_FASTA_OUT = 14,    /* agc_hip_sample_fasta*: segment_copy_kernel + fasta_text_kernel (fasta_out_kernels.hip) */
+    AGC_HIP_K_COUNT = 15
 };
 int agc_hip_timing_enable(agc_hip_ctx *ctx, int on);
 int agc_hip_timing_reset(agc_hip_ctx *ctx);
@@ -331,6 +332,41 @@ int agc_hip_lz_decode_batch(agc_hip_ctx *ctx, uint32_t n, const uint32_t *h_gid,
 /* the same, the decoded symbols left in device memory (d_out: out_cap bytes the caller owns) */
 int agc_hip_lz_decode_batch_dev(agc_hip_ctx *ctx, uint32_t n, const uint32_t *h_gid, const uint8_t *h_enc, const uint64_t *h_enc_off,
                                 const uint8_t *h_rc, uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_off);
+
+/* ---- the read side behind zstd: a sample's FASTA text ------------------------------------------------------ */
+/* Where the symbols of one segment of a contig come from.  RAW: symbol bytes the caller supplies (the raw groups, ids < 16:
+ * CSegment::get_raw, src/common/segment.cpp:136-215); REF: the registered reference of a group as it is (in_group_id 0 of a group
+ * >= 16); DELTA: an LZ-diff delta against the registered reference of its group (CSegment::get, segment.cpp:217-400). */
+enum { AGC_HIP_SEG_RAW = 0, AGC_HIP_SEG_REF = 1, AGC_HIP_SEG_DELTA = 2 };
+typedef struct {
+    uint32_t kind;     /* AGC_HIP_SEG_* */
+    uint32_t gid;      /* REF, DELTA: a registered group */
+    uint64_t off;      /* RAW, DELTA: its bytes are h_bytes[off, off + n_bytes) */
+    uint32_t n_bytes;
+    uint32_t length;   /* symbols the segment must have, overlap included */
+    uint32_t rc;       /* != 0: the segment is read reverse-complemented */
+    uint32_t pad;
+} agc_hip_seg_src;
+
+/* Replaces decompress_contig + the FASTA writer (src/common/agc_decompressor_lib.cpp:172-286) for the whole contigs of one sample,
+ * in one device submission: contig c = the segments [h_ctg_seg[c], h_ctg_seg[c+1]) of h_seg (h_ctg_seg[0] = 0), every segment
+ * oriented by its rc, every segment but a contig's first without its first k symbols; the text of a contig is '>' + its name
+ * (h_names[h_name_off[c], h_name_off[c+1])) + '\n' and its symbols as letters ("ACGTNRYSWKMBDHVU"[code], ' ' for codes >= 16) in
+ * lines of line_length symbols, each followed by '\n' (line_length 0: one line; a contig without symbols: the header only).
+ * *h_text_len always receives the text's size, which follows from the plan alone.  AGC_HIP_ECAP: text_cap is smaller; nothing was
+ * launched or written.  AGC_HIP_ENOREF: a REF / DELTA names a group without a registered reference.  AGC_HIP_EINVAL (nothing is
+ * written to the text; the error text names the segment): a malformed delta (the rules of agc_hip_lz_decode_batch), a delta that
+ * decodes to another number of symbols than `length`, a REF whose reference has another size, a RAW with n_bytes != length, a
+ * segment behind a contig's first with length < k, an unknown kind, off / n_bytes outside h_bytes.  n_ctg == 0: OK, length 0.
+ * Runs on the context's first stream: an encode in flight on a lane goes on beside it.  The text is copied into the caller's
+ * buffer as it is (pinned memory of agc_hip_host_alloc gets the link's rate). */
+int agc_hip_sample_fasta(agc_hip_ctx *ctx, uint32_t n_ctg, const uint64_t *h_ctg_seg, const agc_hip_seg_src *h_seg, const uint8_t *h_bytes,
+                         uint64_t n_bytes, uint32_t k, uint32_t line_length, const char *h_names, const uint64_t *h_name_off,
+                         uint8_t *h_text, uint64_t text_cap, uint64_t *h_text_len);
+/* the same, the text left in device memory (d_text: text_cap bytes the caller owns, any alignment) */
+int agc_hip_sample_fasta_dev(agc_hip_ctx *ctx, uint32_t n_ctg, const uint64_t *h_ctg_seg, const agc_hip_seg_src *h_seg, const uint8_t *h_bytes,
+                             uint64_t n_bytes, uint32_t k, uint32_t line_length, const char *h_names, const uint64_t *h_name_off,
+                             uint8_t *d_text, uint64_t text_cap, uint64_t *h_text_len);
 
 /* Pinned host memory for result buffers (device-to-host copies into pageable memory go through a bounce buffer at a
  * fraction of the link rate).  Freed by agc_hip_host_free or with the context. */

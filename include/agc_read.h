@@ -4,10 +4,14 @@
  * src/lib-cxx/agc-api.h:118-213 (implementation src/lib-cxx/lib-cxx.cpp:123-330), so a program written
  * against the reference's libagc links against this library unchanged.  Host code only: decoding an archive
  * (zstd + LZ-diff decode + reverse complement + stitching) is not part of the GPU hot path.
- * Two additions, marked "extension", return FASTA text the way `agc getset` / `agc getctg` write it.
+ * Two additions, marked "extension", return FASTA text the way `agc getset` / `agc getctg` write it; a third hands out the
+ * PLAN of a sample -- what is left to do behind zstd -- for a caller that assembles the text elsewhere (agc_amd/devread.py: on
+ * the GPU, include/agc_hip.h: agc_hip_sample_fasta).  This library itself stays host code.
  */
 #ifndef AGC_READ_H
 #define AGC_READ_H
+
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -42,6 +46,33 @@ int agc_string_destroy(char *sample);
 char *agc_get_sample_fasta(const agc_t *agc, const char *sample, int line_length, long long *len);
 /* extension: k, min_match_len, pack_cardinality, segment_size stored in the archive; 0 for success */
 int agc_get_params(const agc_t *agc, unsigned *k, unsigned *min_match_len, unsigned *pack_cardinality, unsigned *segment_size);
+
+/* extension: the plan of a whole sample.  Contig c (archive order) has the name names[name_off[c], name_off[c+1]) and the segments
+ * [ctg_seg[c], ctg_seg[c+1]); a segment has its group, its index in the group, its orientation, its length in symbols (the
+ * k-symbol overlap with the segment in front included) and a kind: its symbols are bytes[off, off + seg_bytes) as they are
+ * (AGC_PLAN_RAW: groups < 16), the reference of its group as it is (AGC_PLAN_REF), or the LZ-diff delta bytes[off, off + seg_bytes)
+ * against that reference (AGC_PLAN_DELTA).  groups: the n_groups distinct groups >= 16 the sample needs, ascending; the reference
+ * symbols of groups[i] are ref_bytes[ref_off[i], ref_off[i+1]).  The pointers belong to the plan and live until it is destroyed. */
+enum { AGC_PLAN_RAW = 0, AGC_PLAN_REF = 1, AGC_PLAN_DELTA = 2 };
+typedef struct agc_plan_t agc_plan_t;
+typedef struct {
+    uint64_t n_ctg, n_seg, n_bytes, n_groups;
+    const char *names;
+    const uint64_t *name_off; /* n_ctg + 1 */
+    const uint64_t *ctg_seg;  /* n_ctg + 1 */
+    const uint32_t *group_id, *in_group_id, *rc, *length, *kind, *seg_bytes; /* n_seg each */
+    const uint64_t *off;      /* n_seg */
+    const uint8_t *bytes;     /* n_bytes */
+    const uint32_t *groups;   /* n_groups */
+    const uint64_t *ref_off;  /* n_groups + 1 */
+    const uint8_t *ref_bytes;
+} agc_plan_view;
+/* NULL for an unknown sample or an unreadable archive part */
+agc_plan_t *agc_get_sample_plan(const agc_t *agc, const char *sample);
+/* fills *out; 0 for success */
+int agc_plan_fields(const agc_plan_t *plan, agc_plan_view *out);
+/* frees the plan (NULL: nothing to do); returns 0 */
+int agc_plan_destroy(agc_plan_t *plan);
 
 #ifdef __cplusplus
 }
