@@ -16,6 +16,8 @@ OK, ENODEV, EINVAL, ENOMEM, ECAP, ENOREF = 0, -1, -2, -3, -4, -5
 K_SCAN, K_INDEX, K_ENCODE, K_ESTIMATE, K_COSTVEC, K_REVCOMP, K_PREPROCESS, K_REFSTORE = range(8)
 K_NAMES = ["scan", "index", "encode", "estimate", "costvec", "revcomp", "preprocess", "refstore", "zstd", "filter", "segments", "pack",
            "decode_scan", "decode_write", "fasta_out"]
+K_NAMES_MORE = ["zstd_decode"]  # the slots from 15 on (K_NAMES stays the 15 slots its users count on); timing_get reports both
+ZD_OK, ZD_UNSUPPORTED, ZD_MALFORMED = 0, 1, 2
 SEG_RAW, SEG_REF, SEG_DELTA = 0, 1, 2
 
 # every symbol include/agc_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -38,6 +40,7 @@ SYMBOLS = [
     "agc_hip_lz_split_point_batch_dev", "agc_hip_fetch_slices_dev",
     "agc_hip_ref_lag_counts_dev",
     "agc_hip_zstd17_max_input", "agc_hip_zstd17_resident_frames", "agc_hip_zstd17_batch", "agc_hip_zstd17_batch_dev", "agc_hip_zstd17_background", "agc_hip_zstd17_cparams", "agc_hip_zstd_batch", "agc_hip_zstd_cparams",
+    "agc_hip_zstd_decode_batch", "agc_hip_zstd_decode_batch_dev",
     "agc_hip_packed_words_bytes", "agc_hip_packed_index_bytes", "agc_hip_pack_dev", "agc_hip_expand_dev", "agc_hip_scan_packed_dev",
     "agc_hip_prefetch_packed_dev", "agc_hip_scan_prefetched", "agc_hip_sample_pack", "agc_hip_sample_pack_fasta", "agc_hip_ref_store_begin_packed", "agc_hip_ref_store_end",
     "agc_hip_ref_register_batch_packed", "agc_hip_lz_encode_batch_packed", "agc_hip_lz_encode_begin_packed", "agc_hip_lz_estimate_batch_packed",
@@ -155,6 +158,8 @@ def load():
     L.agc_hip_zstd_cparams.argtypes = [C.c_int, C.c_uint64, u32p]
     L.agc_hip_zstd_batch.argtypes = [vp, C.c_uint32, u8p, u64p, u8p, u8p, C.c_uint64, u64p]
     L.agc_hip_zstd17_batch_dev.argtypes = [vp, C.c_uint32, vp, u64p, u8p, C.c_uint64, u64p]
+    L.agc_hip_zstd_decode_batch.argtypes = [vp, C.c_uint32, u8p, u64p, u8p, C.c_uint64, u64p, u32p]
+    L.agc_hip_zstd_decode_batch_dev.argtypes = [vp, C.c_uint32, u8p, u64p, vp, C.c_uint64, u64p, u32p]
     L.agc_hip_zstd17_background.argtypes = [vp, C.c_int]
     L.agc_hip_zstd17_max_input.restype = C.c_uint32
     L.agc_hip_zstd17_resident_frames.argtypes = [vp]
@@ -250,7 +255,7 @@ class Context:
 
     def timing_get(self):
         out = {}
-        for i, n in enumerate(K_NAMES):
+        for i, n in enumerate(K_NAMES + K_NAMES_MORE):
             ms = C.c_double()
             ln = C.c_uint64()
             self._chk(self.L.agc_hip_timing_get(self.h, i, C.byref(ms), C.byref(ln)))
@@ -756,6 +761,45 @@ class Context:
         doff = np.zeros(n + 1, np.uint64)
         self._chk(self.L.agc_hip_zstd_batch(self.h, n, _p(src, u8p), _p(off, u64p), _p(lv, u8p), _p(dst, u8p), cap, _p(doff, u64p)))
         return [dst[int(doff[i]):int(doff[i + 1])].tobytes() for i in range(n)]
+
+    def _zd_args(self, frames):
+        if isinstance(frames, tuple):  # (src, off): the frames back to back already, frame s = src[off[s]:off[s+1]]
+            src, off = _a(frames[0], np.uint8), _a(frames[1], np.uint64)
+            n = off.size - 1
+            return n, (src if src.size else np.zeros(1, np.uint8)), off, np.zeros(n + 1, np.uint64), np.full(n, 0xFFFFFFFF, np.uint32)
+        n = len(frames)
+        off = np.zeros(n + 1, np.uint64)
+        off[1:] = np.cumsum([len(x) for x in frames])
+        src = np.frombuffer(b"".join(bytes(x) for x in frames), np.uint8) if off[-1] else np.zeros(1, np.uint8)
+        return n, src, off, np.zeros(n + 1, np.uint64), np.full(n, 0xFFFFFFFF, np.uint32)
+
+    def zstd_decode_batch_raw(self, frames, out_ptr, out_cap, dev=False):
+        """the entry point itself (agc_hip_zstd_decode_batch, dev: _dev) -> (return code, out_off[n+1], statuses[n]); frames: a list of
+        bytes-like, or (src, off) with the frames back to back"""
+        n, src, off, ooff, st = self._zd_args(frames)
+        fn = self.L.agc_hip_zstd_decode_batch_dev if dev else self.L.agc_hip_zstd_decode_batch
+        rc_ = fn(self.h, n, _p(src, u8p), _p(off, u64p), out_ptr, int(out_cap), _p(ooff, u64p), _p(st, u32p))
+        return rc_, ooff, st
+
+    def zstd_decode_batch(self, frames):
+        """zstd frames (list of bytes-like, or (src, off) as zstd_decode_batch_raw takes them) -> (list of their decoded bytes, statuses): statuses[s] is 0 or ZD_UNSUPPORTED /
+        ZD_MALFORMED, and the bytes of such a frame are None.  A frame is refused on its own: the others of the batch are decoded."""
+        rc_, ooff, st = self.zstd_decode_batch_raw(frames, None, 0)
+        if rc_ == ECAP:  # (the first call sized the output from the frame headers: nothing was launched)
+            out = np.empty(int(ooff[-1]), np.uint8)
+            rc_, ooff, st = self.zstd_decode_batch_raw(frames, _p(out, u8p), out.size)
+        else:
+            out = np.zeros(0, np.uint8)
+        if rc_ != EINVAL or not st.any():
+            self._chk(rc_)
+        return [None if st[i] else out[int(ooff[i]):int(ooff[i + 1])].tobytes() for i in range(st.size)], st
+
+    def zstd_decode_batch_dev(self, frames, d_out, out_cap):
+        """the same, the bytes left at the device address d_out (out_cap bytes) -> (out_off[n+1], statuses)"""
+        rc_, ooff, st = self.zstd_decode_batch_raw(frames, d_out, out_cap, dev=True)
+        if rc_ != EINVAL or not st.any():
+            self._chk(rc_)
+        return ooff, st
 
     def zstd17_batch_raw(self, src, off):
         """packs back to back (pack i = src[off[i]:off[i+1]]) -> (frames back to back, their offsets [n + 1]); no per-pack

@@ -23,6 +23,7 @@
 #include "lz_decode_kernels.hip"
 #include "fasta_out_kernels.hip"
 #include "zstd_kernels.hip"
+#include "zstd_decode_kernels.hip"
 
 using namespace agc;
 
@@ -157,6 +158,7 @@ struct agc_hip_ctx {
         d_jobs, d_counts, d_in, d_pp_cnt, d_pp_off, d_pp_total, d_lag, d_sample, d_zsrc, d_zdst, d_zws, d_zjobs, d_zsize, d_zout, d_zdstoff, d_maybe, d_fjobs;
     DevBuf d_dec_enc, d_dec_jobs, d_dec_res, d_dec_out; // agc_hip_lz_decode_batch*: the deltas, their descriptors, lengths + status, the symbols
     DevBuf d_fa_sym, d_fa_copy, d_fa_plan, d_fa_text;   // agc_hip_sample_fasta*: the sample's symbols, the copy jobs, the text plan, the text
+    DevBuf d_zd_src, d_zd_jobs, d_zd_status, d_zd_ws, d_zd_out; // agc_hip_zstd_decode_batch*: the frames, their descriptors, their statuses, the literals workspaces, the bytes
 
     PackTemp pk1;        // byte-input entry points on the first stream
     PackTemp pk_sample;  // agc_hip_sample_pack
@@ -3266,6 +3268,99 @@ int agc_hip_zstd17_batch_dev(agc_hip_ctx *c, uint32_t n, const uint8_t *d_src, c
     if (n && h_src_off && h_src_off[n] > h_src_off[0] && !d_src)
         return AGC_HIP_EINVAL;
     return zstd17_batch_impl(c, n, nullptr, d_src ? d_src : (const uint8_t *)1, h_src_off, h_dst, dst_cap, h_dst_off);
+}
+
+// The decode (include/agc_hip.h) on the first stream.  The host reads every frame header: that sizes the output, and a frame whose
+// header is refused never reaches the decoder.  zstd_decode_kernel then gives every other frame a wave, its slice of the output and
+// its slice of the literals workspace (min(content size, 128 KiB): what a block's literals can need).
+// d_out: the caller's device buffer, or nullptr: the context's, copied to h_out.
+static int zstd_decode_impl(agc_hip_ctx *c, uint32_t n, const uint8_t *h_src, const uint64_t *h_src_off, uint8_t *h_out, uint8_t *d_out, uint64_t out_cap,
+                            uint64_t *h_out_off, uint32_t *h_status)
+{
+    for (uint32_t i = 0; i < n; ++i)
+        if (h_src_off[i + 1] < h_src_off[i]) {
+            c->err = "zstd_decode: frame " + std::to_string(i) + " ends in front of its start";
+            return AGC_HIP_EINVAL;
+        }
+    const uint64_t s0 = h_src_off[0], src_bytes = h_src_off[n] - s0;
+    std::vector<ZDecJob> jobs(n);
+    uint64_t tot = 0, ws_tot = 0;
+    uint32_t n_live = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t len = h_src_off[i + 1] - h_src_off[i];
+        const zs::dec::FrameHeader h = zs::dec::parseFrameHeader(h_src + h_src_off[i], len);
+        const uint32_t ws_len = (std::min(h.contentSize, zs::BLOCKSIZE_MAX) + 15u) & ~15u;
+        jobs[i] = {h_src_off[i] - s0, tot, ws_tot, (uint32_t)len, h.contentSize, ws_len, h.status};
+        h_out_off[i] = tot;
+        tot += h.contentSize;
+        ws_tot += ws_len;
+        n_live += h.status == zs::dec::OK;
+        if (h_status)
+            h_status[i] = h.status;
+    }
+    h_out_off[n] = tot;
+    if (tot > out_cap) {
+        c->err = "zstd_decode: the output buffer holds " + std::to_string(out_cap) + " bytes, " + std::to_string(tot) + " are needed";
+        return AGC_HIP_ECAP;
+    }
+    std::vector<uint32_t> status(n);
+    if (n_live) {
+        HIPCHK(c, hipSetDevice(c->device));
+        CHK(ensure(c, c->d_zd_src, src_bytes + 64));
+        CHK(ensure(c, c->d_zd_jobs, (size_t)n * sizeof(ZDecJob)));
+        CHK(ensure(c, c->d_zd_status, (size_t)n * sizeof(uint32_t)));
+        CHK(ensure(c, c->d_zd_ws, ws_tot + 64));
+        if (!d_out) {
+            CHK(ensure(c, c->d_zd_out, tot + 64));
+            d_out = (uint8_t *)c->d_zd_out.p;
+        }
+        CHK(upload(c, c->d_zd_src.p, h_src + s0, src_bytes, c->stream));
+        CHK(upload(c, c->d_zd_jobs.p, jobs.data(), (size_t)n * sizeof(ZDecJob), c->stream));
+        {
+            KTimer t(c, AGC_HIP_K_ZSTD_DECODE);
+            hipLaunchKernelGGL(zstd_decode_kernel, dim3(n), dim3(WAVE), 0, c->stream, (const ZDecJob *)c->d_zd_jobs.p, n, (const uint8_t *)c->d_zd_src.p, d_out,
+                               (uint8_t *)c->d_zd_ws.p, (uint32_t *)c->d_zd_status.p); // a wave per frame
+        }
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(status.data(), c->d_zd_status.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (h_out && tot)
+            HIPCHK(c, hipMemcpyAsync(h_out, d_out, tot, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else
+        for (uint32_t i = 0; i < n; ++i)
+            status[i] = jobs[i].status;
+    for (uint32_t i = 0; i < n; ++i)
+        if (h_status)
+            h_status[i] = status[i];
+    for (uint32_t i = 0; i < n; ++i)
+        if (status[i] != zs::dec::OK) {
+            c->err = "zstd_decode: frame " + std::to_string(i) + " is refused: " + (status[i] == zs::dec::UNSUPPORTED ? "unsupported (status 1)" : "malformed (status 2)");
+            return AGC_HIP_EINVAL;
+        }
+    return AGC_HIP_OK;
+}
+
+int agc_hip_zstd_decode_batch(agc_hip_ctx *c, uint32_t n, const uint8_t *h_src, const uint64_t *h_src_off, uint8_t *h_out, uint64_t out_cap, uint64_t *h_out_off,
+                              uint32_t *h_status)
+{
+    if (!c || !h_out_off || (n && (!h_src_off || (h_src_off[n] > h_src_off[0] && !h_src))) || (out_cap && !h_out))
+        return AGC_HIP_EINVAL;
+    h_out_off[0] = 0;
+    if (!n)
+        return AGC_HIP_OK;
+    return zstd_decode_impl(c, n, h_src, h_src_off, h_out, nullptr, out_cap, h_out_off, h_status);
+}
+
+int agc_hip_zstd_decode_batch_dev(agc_hip_ctx *c, uint32_t n, const uint8_t *h_src, const uint64_t *h_src_off, uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_off,
+                                  uint32_t *h_status)
+{
+    if (!c || !h_out_off || (n && (!h_src_off || (h_src_off[n] > h_src_off[0] && !h_src))) || (out_cap && !d_out))
+        return AGC_HIP_EINVAL;
+    h_out_off[0] = 0;
+    if (!n)
+        return AGC_HIP_OK;
+    // (an output of 0 bytes: the context's buffer stands in for a d_out the caller did not have to give)
+    return zstd_decode_impl(c, n, h_src, h_src_off, nullptr, d_out, out_cap, h_out_off, h_status);
 }
 
 } // extern "C"

@@ -63,7 +63,8 @@ enum {
     AGC_HIP_K_DECODE_SCAN = 12,  /* lz_decode_scan_kernel: length and status of every delta (lz_decode_kernels.hip) */
     AGC_HIP_K_DECODE_WRITE = 13, /* lz_decode_write_kernel: the decoded symbols */
     AGC_HIP_K_FASTA_OUT = 14,    /* agc_hip_sample_fasta*: segment_copy_kernel + fasta_text_kernel (fasta_out_kernels.hip) */
-    AGC_HIP_K_COUNT = 15
+    AGC_HIP_K_ZSTD_DECODE = 15,  /* agc_hip_zstd_decode_batch*: zstd_decode_kernel (zstd_decode_kernels.hip) */
+    AGC_HIP_K_COUNT = 16
 };
 int agc_hip_timing_enable(agc_hip_ctx *ctx, int on);
 int agc_hip_timing_reset(agc_hip_ctx *ctx);
@@ -492,6 +493,29 @@ uint32_t agc_hip_zstd17_resident_frames(agc_hip_ctx *ctx);
  * windowLog, chainLog, hashLog, searchLog, minMatch, targetLength, strategy.  Exposed so that tests can pin them. */
 int agc_hip_zstd17_cparams(uint64_t src_size, uint32_t out7[7]);
 int agc_hip_zstd_cparams(int level /* 13, 17, 19 */, uint64_t src_size, uint32_t out7[7]);
+
+/* The other direction.  Replaces ZSTD_decompressDCtx as CSegment::get_raw / get call it (src/common/segment.cpp:136-400) for a
+ * batch of frames.  frame s = h_src[h_src_off[s] .. h_src_off[s+1]); decoded s = out[h_out_off[s] .. h_out_off[s+1]);
+ * h_status[s] = 0 or AGC_HIP_ZD_* (h_status may be NULL).  A frame is one zstd frame as ZSTD_compressCCtx writes it: content size
+ * in the header, any number of blocks, no dictionary, no checksum (what is decoded and what is refused: agc_amd/csrc/zstd/
+ * zs_decode.h).  The host reads the frame headers and fills h_out_off[0..n] before anything is launched: a frame whose header is
+ * refused has size 0 and its status.  AGC_HIP_ECAP: out_cap is smaller than h_out_off[n]; nothing was launched or written.
+ * AGC_HIP_EINVAL: at least one frame has a status != 0 (the error text names the first and its status); the kernel ran for the
+ * frames whose headers were accepted (when every header is refused nothing is launched), the frames with status 0 are complete
+ * and correct, the output range of a refused frame has unspecified contents, no byte outside the frames' ranges is written.
+ * AGC_HIP_EINVAL as well, with nothing but h_out_off[0] = 0 filled and nothing launched: an h_src_off that decreases, a NULL that
+ * is needed.  AGC_HIP_OK: every frame has status 0.  n == 0: OK.  Runs on the context's first stream: an encode in flight on a
+ * lane goes on beside it. */
+enum {
+    AGC_HIP_ZD_OK = 0,
+    AGC_HIP_ZD_UNSUPPORTED = 1, /* a frame without a content size, with a dictionary id != 0 or a checksum, a skippable frame, >= 2^31 bytes */
+    AGC_HIP_ZD_MALFORMED = 2    /* not a frame of the format: wrong magic, truncated, bytes left over, tables, offsets or lengths that cannot be */
+};
+int agc_hip_zstd_decode_batch(agc_hip_ctx *ctx, uint32_t n, const uint8_t *h_src, const uint64_t *h_src_off, uint8_t *h_out, uint64_t out_cap,
+                              uint64_t *h_out_off, uint32_t *h_status);
+/* the same, the decoded bytes left in device memory (d_out: out_cap bytes the caller owns) */
+int agc_hip_zstd_decode_batch_dev(agc_hip_ctx *ctx, uint32_t n, const uint8_t *h_src, const uint64_t *h_src_off, uint8_t *d_out, uint64_t out_cap,
+                                  uint64_t *h_out_off, uint32_t *h_status);
 
 #ifdef __cplusplus
 }
