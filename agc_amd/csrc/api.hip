@@ -2,6 +2,9 @@
 // Host-side logic here is orchestration only (buffer management, sorting sparse hit
 // lists, sizing tables with the reference's double arithmetic); all symbol-level work is
 // done by the kernels in scan_kernels.hip / lz_kernels.hip.  There is no CPU fallback.
+// This file: the context, the helpers every entry point shares (ensure, upload, KTimer, ...) and the create path.  The read path
+// (LZ decode, a sample's FASTA text, zstd decode) is read_api.hip, included at the end with splitters.hip and segments.hip: the
+// library stays one translation unit.
 #include "../../include/agc_hip.h"
 #include "dev_common.h"
 
@@ -156,9 +159,11 @@ struct agc_hip_ctx {
     } seg_state;
     DevBuf d_ranges, d_hits, d_counter, d_segs, d_slices, d_scratch, d_resv, d_resp, d_dstoff, d_compact,
         d_jobs, d_counts, d_in, d_pp_cnt, d_pp_off, d_pp_total, d_lag, d_sample, d_zsrc, d_zdst, d_zws, d_zjobs, d_zsize, d_zout, d_zdstoff, d_maybe, d_fjobs;
-    DevBuf d_dec_enc, d_dec_jobs, d_dec_res, d_dec_out; // agc_hip_lz_decode_batch*: the deltas, their descriptors, lengths + status, the symbols
-    DevBuf d_fa_sym, d_fa_copy, d_fa_plan, d_fa_text;   // agc_hip_sample_fasta*: the sample's symbols, the copy jobs, the text plan, the text
-    DevBuf d_zd_src, d_zd_jobs, d_zd_status, d_zd_ws, d_zd_out; // agc_hip_zstd_decode_batch*: the frames, their descriptors, their statuses, the literals workspaces, the bytes
+    struct ReadBufs { // the read path (read_api.hip)
+        DevBuf d_dec_enc, d_dec_jobs, d_dec_res, d_dec_out; // agc_hip_lz_decode_batch*: the deltas, their descriptors, lengths + status, the symbols
+        DevBuf d_fa_sym, d_fa_copy, d_fa_plan, d_fa_text;   // agc_hip_sample_fasta*: the sample's symbols, the copy jobs, the text plan, the text
+        DevBuf d_zd_src, d_zd_jobs, d_zd_status, d_zd_ws, d_zd_out; // agc_hip_zstd_decode_batch*: the frames, their descriptors, their statuses, the literals workspaces, the bytes
+    } rd;
 
     PackTemp pk1;        // byte-input entry points on the first stream
     PackTemp pk_sample;  // agc_hip_sample_pack
@@ -2230,244 +2235,6 @@ static int lz_encode_begin_enter(agc_hip_ctx *c, int lane, uint32_t n)
     return AGC_HIP_OK;
 }
 
-// The decode (include/agc_hip.h) on the first stream: lz_decode_scan_kernel gives every delta's length and status, the host lays
-// the output out, lz_decode_write_kernel fills it -- launched only when every delta of the batch is well formed.
-// d_out: the caller's device buffer, or nullptr: the context's, copied to h_out.
-static int lz_decode_impl(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const uint8_t *h_enc, const uint64_t *h_enc_off, const uint8_t *h_rc,
-                          uint8_t *h_out, uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_off)
-{
-    for (uint32_t i = 0; i < n; ++i) {
-        if (h_gid[i] >= c->refs.size() || !c->refs[h_gid[i]].valid) {
-            c->err = "lz_decode: delta " + std::to_string(i) + ": group " + std::to_string(h_gid[i]) + " has no registered reference";
-            return AGC_HIP_EINVAL;
-        }
-        if (h_enc_off[i + 1] < h_enc_off[i]) {
-            c->err = "lz_decode: delta " + std::to_string(i) + " ends in front of its start";
-            return AGC_HIP_EINVAL;
-        }
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    CHK(upload_refs(c));
-    const uint64_t e0 = h_enc_off[0], enc_bytes = h_enc_off[n] - e0;
-    std::vector<DecodeJob> jobs(n);
-    for (uint32_t i = 0; i < n; ++i)
-        jobs[i] = {h_enc_off[i] - e0, h_enc_off[i + 1] - h_enc_off[i], 0, 0, h_gid[i], h_rc && h_rc[i] ? 1u : 0u, 0};
-    CHK(ensure(c, c->d_dec_enc, enc_bytes + 64));
-    CHK(ensure(c, c->d_dec_jobs, (size_t)n * sizeof(DecodeJob)));
-    CHK(ensure(c, c->d_dec_res, (size_t)n * sizeof(DecodeResult)));
-    if (enc_bytes)
-        CHK(upload(c, c->d_dec_enc.p, h_enc + e0, enc_bytes, c->stream));
-    CHK(upload(c, c->d_dec_jobs.p, jobs.data(), (size_t)n * sizeof(DecodeJob), c->stream));
-    const dim3 grid((n + 3) / 4), block(4 * WAVE); // a wave per delta
-    {
-        KTimer t(c, AGC_HIP_K_DECODE_SCAN);
-        hipLaunchKernelGGL(lz_decode_scan_kernel, grid, block, 0, c->stream, (const RefDesc *)c->d_refs.p, (const DecodeJob *)c->d_dec_jobs.p, n,
-                           (const uint8_t *)c->d_dec_enc.p, (DecodeResult *)c->d_dec_res.p);
-    }
-    HIPCHK(c, hipGetLastError());
-    std::vector<DecodeResult> res(n);
-    HIPCHK(c, hipMemcpyAsync(res.data(), c->d_dec_res.p, (size_t)n * sizeof(DecodeResult), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (uint32_t i = 0; i < n; ++i)
-        if (res[i].status != lzd::OK) {
-            static const char *why[] = {"", "a truncated or malformed token", "'!' at or past the end of the reference", "a match outside the reference",
-                                        "more than 2^32 - 1 decoded symbols"};
-            c->err = "lz_decode: delta " + std::to_string(i) + " is rejected: " + why[res[i].status <= lzd::TOO_LONG ? res[i].status : 1];
-            return AGC_HIP_EINVAL;
-        }
-    uint64_t tot = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        h_out_off[i] = tot;
-        jobs[i].out_off = tot;
-        jobs[i].out_len = res[i].len;
-        tot += res[i].len;
-    }
-    h_out_off[n] = tot;
-    if (tot > out_cap) {
-        c->err = "lz_decode: the output buffer holds " + std::to_string(out_cap) + " bytes, " + std::to_string(tot) + " are needed";
-        return AGC_HIP_ECAP;
-    }
-    if (!tot)
-        return AGC_HIP_OK;
-    if (!d_out) {
-        CHK(ensure(c, c->d_dec_out, tot + 64));
-        d_out = (uint8_t *)c->d_dec_out.p;
-    }
-    CHK(upload(c, c->d_dec_jobs.p, jobs.data(), (size_t)n * sizeof(DecodeJob), c->stream)); // (now with where each delta's symbols go)
-    {
-        KTimer t(c, AGC_HIP_K_DECODE_WRITE);
-        hipLaunchKernelGGL(lz_decode_write_kernel, grid, block, 0, c->stream, (const RefDesc *)c->d_refs.p, (const DecodeJob *)c->d_dec_jobs.p, n,
-                           (const uint8_t *)c->d_dec_enc.p, d_out);
-    }
-    HIPCHK(c, hipGetLastError());
-    if (h_out)
-        HIPCHK(c, hipMemcpyAsync(h_out, d_out, tot, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return AGC_HIP_OK;
-}
-
-// The FASTA text of a sample (include/agc_hip.h) on the first stream.  The layout -- and with it the text's size -- follows from the
-// plan alone; then every segment is checked (the deltas by lz_decode_scan_kernel, against the length the plan declares) before
-// anything is written: lz_decode_write_kernel and segment_copy_kernel lay the segments out in the symbol buffer, fasta_text_kernel
-// writes the text.  d_text: the caller's device buffer, or nullptr: the context's, copied to h_text.
-static int sample_fasta_impl(agc_hip_ctx *c, uint32_t n_ctg, const uint64_t *h_ctg_seg, const agc_hip_seg_src *h_seg, const uint8_t *h_bytes, uint64_t n_bytes,
-                             uint32_t k, uint32_t line_length, const char *h_names, const uint64_t *h_name_off, uint8_t *h_text, uint8_t *d_text,
-                             uint64_t text_cap, uint64_t *h_text_len)
-{
-    *h_text_len = 0;
-    if (!n_ctg)
-        return AGC_HIP_OK;
-    const uint64_t n_seg = h_ctg_seg[n_ctg];
-    bool ascending = h_ctg_seg[0] == 0 && n_seg <= 0xFFFFFFFFull;
-    for (uint32_t ci = 0; ci < n_ctg; ++ci)
-        ascending = ascending && h_ctg_seg[ci] <= h_ctg_seg[ci + 1] && h_ctg_seg[ci + 1] <= n_seg && h_name_off[ci] <= h_name_off[ci + 1];
-    if (!ascending) {
-        c->err = "sample_fasta: the contigs' segment ranges or name offsets do not ascend from 0";
-        return AGC_HIP_EINVAL;
-    }
-    std::vector<uint64_t> ctg_text(n_ctg + 1), ctg_sym(n_ctg), seg_start(n_seg), seg_off(n_seg);
-    std::vector<uint32_t> skip(n_seg);
-    std::vector<DecodeJob> dj;
-    std::vector<uint32_t> dj_seg;
-    std::vector<CopyJob> cj;
-    int bad = AGC_HIP_OK; // the first complaint; reported once the text's size is known
-    uint64_t sym_total = 0, text = 0;
-    for (uint32_t ci = 0; ci < n_ctg; ++ci) {
-        uint64_t pos = 0;
-        for (uint64_t s = h_ctg_seg[ci]; s < h_ctg_seg[ci + 1]; ++s) {
-            const agc_hip_seg_src &g = h_seg[s];
-            const uint32_t sk = s == h_ctg_seg[ci] ? 0 : k;
-            const char *why = nullptr;
-            int code = AGC_HIP_EINVAL;
-            if (g.kind > AGC_HIP_SEG_DELTA)
-                why = "has an unknown kind";
-            else if (g.kind != AGC_HIP_SEG_REF && (g.off > n_bytes || g.n_bytes > n_bytes - g.off))
-                why = "names bytes outside the byte buffer";
-            else if (g.kind == AGC_HIP_SEG_RAW && g.n_bytes != g.length)
-                why = "is raw and its byte count differs from its length";
-            else if (g.kind != AGC_HIP_SEG_RAW && (g.gid >= c->refs.size() || !c->refs[g.gid].valid))
-                why = "names a group without a registered reference", code = AGC_HIP_ENOREF;
-            else if (g.kind == AGC_HIP_SEG_REF && c->refs[g.gid].ref_size != g.length)
-                why = "is a reference whose size differs from its length";
-            else if (g.length < sk)
-                why = "is shorter than the overlap with the segment in front of it";
-            if (why && bad == AGC_HIP_OK) {
-                c->err = "sample_fasta: segment " + std::to_string(s) + " (contig " + std::to_string(ci) + ") " + why;
-                bad = code;
-            }
-            seg_start[s] = pos;
-            seg_off[s] = sym_total;
-            skip[s] = sk;
-            if (!why && g.kind == AGC_HIP_SEG_DELTA) {
-                dj.push_back({g.off, g.n_bytes, sym_total, g.length, g.gid, g.rc ? 1u : 0u, 0});
-                dj_seg.push_back((uint32_t)s);
-            } else if (!why && g.length)
-                cj.push_back({g.off, sym_total, g.length, g.gid, g.rc ? 1u : 0u, g.kind == AGC_HIP_SEG_REF ? 1u : 0u});
-            pos += g.length >= sk ? g.length - sk : 0;
-            sym_total += g.length;
-        }
-        ctg_sym[ci] = pos;
-        ctg_text[ci] = text;
-        text += fo::contig_text_bytes(h_name_off[ci + 1] - h_name_off[ci], pos, line_length);
-    }
-    ctg_text[n_ctg] = text;
-    *h_text_len = text;
-    if (bad != AGC_HIP_OK)
-        return bad;
-    if (text > text_cap) {
-        c->err = "sample_fasta: the text buffer holds " + std::to_string(text_cap) + " bytes, " + std::to_string(text) + " are needed";
-        return AGC_HIP_ECAP;
-    }
-    const uint32_t a = d_text ? (uint32_t)((uintptr_t)d_text & (fo::CHUNK - 1)) : 0;
-    const uint64_t n_chunks = fo::chunk_count(a, text), text_blocks = (n_chunks + 255) / 256;
-    if (text_blocks > 0x7FFFFFFFull) {
-        c->err = "sample_fasta: a text of " + std::to_string(text) + " bytes is more than one launch writes";
-        return AGC_HIP_EINVAL;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    CHK(upload_refs(c));
-    CHK(ensure(c, c->d_dec_enc, n_bytes + 64));
-    if (n_bytes)
-        CHK(upload(c, c->d_dec_enc.p, h_bytes, n_bytes, c->stream));
-    const dim3 block(4 * WAVE); // a wave per segment
-    const uint32_t n_dj = (uint32_t)dj.size(), n_cj = (uint32_t)cj.size();
-    if (n_dj) {
-        CHK(ensure(c, c->d_dec_jobs, (size_t)n_dj * sizeof(DecodeJob)));
-        CHK(ensure(c, c->d_dec_res, (size_t)n_dj * sizeof(DecodeResult)));
-        CHK(upload(c, c->d_dec_jobs.p, dj.data(), (size_t)n_dj * sizeof(DecodeJob), c->stream));
-        {
-            KTimer t(c, AGC_HIP_K_DECODE_SCAN);
-            hipLaunchKernelGGL(lz_decode_scan_kernel, dim3((n_dj + 3) / 4), block, 0, c->stream, (const RefDesc *)c->d_refs.p, (const DecodeJob *)c->d_dec_jobs.p, n_dj,
-                               (const uint8_t *)c->d_dec_enc.p, (DecodeResult *)c->d_dec_res.p);
-        }
-        HIPCHK(c, hipGetLastError());
-        std::vector<DecodeResult> res(n_dj);
-        HIPCHK(c, hipMemcpyAsync(res.data(), c->d_dec_res.p, (size_t)n_dj * sizeof(DecodeResult), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (uint32_t i = 0; i < n_dj; ++i)
-            if (res[i].status != lzd::OK || res[i].len != dj[i].out_len) {
-                c->err = "sample_fasta: segment " + std::to_string(dj_seg[i]) +
-                         (res[i].status != lzd::OK ? " has a malformed delta" : " decodes to " + std::to_string(res[i].len) + " symbols, its length says " + std::to_string(dj[i].out_len));
-                return AGC_HIP_EINVAL;
-            }
-    }
-    // every segment has passed: from here on things are written
-    CHK(ensure(c, c->d_fa_sym, sym_total + 64));
-    uint8_t *d_sym = c->d_fa_sym.as<uint8_t>();
-    if (n_dj) {
-        KTimer t(c, AGC_HIP_K_DECODE_WRITE);
-        hipLaunchKernelGGL(lz_decode_write_kernel, dim3((n_dj + 3) / 4), block, 0, c->stream, (const RefDesc *)c->d_refs.p, (const DecodeJob *)c->d_dec_jobs.p, n_dj,
-                           (const uint8_t *)c->d_dec_enc.p, d_sym);
-    }
-    HIPCHK(c, hipGetLastError());
-    if (n_cj) {
-        CHK(ensure(c, c->d_fa_copy, (size_t)n_cj * sizeof(CopyJob)));
-        CHK(upload(c, c->d_fa_copy.p, cj.data(), (size_t)n_cj * sizeof(CopyJob), c->stream));
-        KTimer t(c, AGC_HIP_K_FASTA_OUT);
-        hipLaunchKernelGGL(segment_copy_kernel, dim3((n_cj + 3) / 4), block, 0, c->stream, (const RefDesc *)c->d_refs.p, (const CopyJob *)c->d_fa_copy.p, n_cj,
-                           (const uint8_t *)c->d_dec_enc.p, d_sym);
-    }
-    HIPCHK(c, hipGetLastError());
-    // the plan in one upload: the 64-bit arrays, the 32-bit one, the names
-    const uint64_t names0 = h_name_off[0], names_bytes = h_name_off[n_ctg] - names0;
-    const size_t o_ctg_text = 0, o_ctg_seg = o_ctg_text + 8 * ((size_t)n_ctg + 1), o_ctg_sym = o_ctg_seg + 8 * ((size_t)n_ctg + 1), o_name_off = o_ctg_sym + 8 * (size_t)n_ctg,
-                 o_seg_start = o_name_off + 8 * ((size_t)n_ctg + 1), o_seg_off = o_seg_start + 8 * n_seg, o_skip = o_seg_off + 8 * n_seg, o_names = o_skip + 4 * n_seg,
-                 plan_bytes = o_names + names_bytes;
-    std::vector<uint8_t> plan(plan_bytes);
-    std::vector<uint64_t> name_off(h_name_off, h_name_off + n_ctg + 1);
-    for (uint64_t &o : name_off)
-        o -= names0;
-    std::memcpy(plan.data() + o_ctg_text, ctg_text.data(), 8 * ((size_t)n_ctg + 1));
-    std::memcpy(plan.data() + o_ctg_seg, h_ctg_seg, 8 * ((size_t)n_ctg + 1));
-    std::memcpy(plan.data() + o_ctg_sym, ctg_sym.data(), 8 * (size_t)n_ctg);
-    std::memcpy(plan.data() + o_name_off, name_off.data(), 8 * ((size_t)n_ctg + 1));
-    if (n_seg) {
-        std::memcpy(plan.data() + o_seg_start, seg_start.data(), 8 * n_seg);
-        std::memcpy(plan.data() + o_seg_off, seg_off.data(), 8 * n_seg);
-        std::memcpy(plan.data() + o_skip, skip.data(), 4 * n_seg);
-    }
-    if (names_bytes)
-        std::memcpy(plan.data() + o_names, h_names + names0, names_bytes);
-    CHK(ensure(c, c->d_fa_plan, plan_bytes + 64));
-    CHK(upload(c, c->d_fa_plan.p, plan.data(), plan_bytes, c->stream));
-    if (!d_text) {
-        CHK(ensure(c, c->d_fa_text, text + 64));
-        d_text = c->d_fa_text.as<uint8_t>();
-    }
-    const uint8_t *pl = c->d_fa_plan.as<uint8_t>();
-    const TextPlan P = {(g_u64 *)(pl + o_ctg_text), (g_u64 *)(pl + o_ctg_seg), (g_u64 *)(pl + o_ctg_sym), (g_u64 *)(pl + o_name_off), (g_u8 *)(pl + o_names),
-                        (g_u64 *)(pl + o_seg_start), (g_u64 *)(pl + o_seg_off), (g_u32 *)(pl + o_skip), (g_u8 *)d_sym, n_ctg, line_length};
-    {
-        KTimer t(c, AGC_HIP_K_FASTA_OUT);
-        hipLaunchKernelGGL(fasta_text_kernel, dim3((uint32_t)text_blocks), dim3(256), 0, c->stream, P, d_text, a, text, n_chunks);
-    }
-    HIPCHK(c, hipGetLastError());
-    if (h_text)
-        HIPCHK(c, hipMemcpyAsync(h_text, d_text, text, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return AGC_HIP_OK;
-}
-
 extern "C" {
 
 int agc_hip_lz_encode_batch_packed(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const agc_hip_packed *pk, const uint64_t *h_off,
@@ -2620,44 +2387,6 @@ int agc_hip_lz_encode_end_on(agc_hip_ctx *c, uint32_t lane, uint8_t *h_enc, uint
     CHK(collect_deltas(c, {L.d_scratch, L.d_segs, L.d_resv, L.d_dstoff, L.d_compact}, L.s, n, L.h_lens.as<uint32_t>(), true, h_enc, enc_cap, h_enc_off, Laps("lz_encode_end", n)));
     L.pending = false;
     return AGC_HIP_OK;
-}
-
-int agc_hip_lz_decode_batch(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const uint8_t *h_enc, const uint64_t *h_enc_off, const uint8_t *h_rc,
-                            uint8_t *h_out, uint64_t out_cap, uint64_t *h_out_off)
-{
-    if (!c || !h_out_off || (n && (!h_gid || !h_enc_off || (h_enc_off[n] > h_enc_off[0] && !h_enc))) || (out_cap && !h_out))
-        return AGC_HIP_EINVAL;
-    h_out_off[0] = 0;
-    if (!n)
-        return AGC_HIP_OK;
-    return lz_decode_impl(c, n, h_gid, h_enc, h_enc_off, h_rc, h_out, nullptr, out_cap, h_out_off);
-}
-
-int agc_hip_lz_decode_batch_dev(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const uint8_t *h_enc, const uint64_t *h_enc_off, const uint8_t *h_rc,
-                                uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_off)
-{
-    if (!c || !h_out_off || (n && (!h_gid || !h_enc_off || (h_enc_off[n] > h_enc_off[0] && !h_enc))) || (out_cap && !d_out))
-        return AGC_HIP_EINVAL;
-    h_out_off[0] = 0;
-    if (!n)
-        return AGC_HIP_OK;
-    return lz_decode_impl(c, n, h_gid, h_enc, h_enc_off, h_rc, nullptr, d_out, out_cap, h_out_off);
-}
-
-int agc_hip_sample_fasta(agc_hip_ctx *c, uint32_t n_ctg, const uint64_t *h_ctg_seg, const agc_hip_seg_src *h_seg, const uint8_t *h_bytes, uint64_t n_bytes, uint32_t k,
-                         uint32_t line_length, const char *h_names, const uint64_t *h_name_off, uint8_t *h_text, uint64_t text_cap, uint64_t *h_text_len)
-{
-    if (!c || !h_text_len || (n_ctg && (!h_ctg_seg || !h_name_off || (h_ctg_seg[n_ctg] && !h_seg) || (n_bytes && !h_bytes))) || (text_cap && !h_text))
-        return AGC_HIP_EINVAL;
-    return sample_fasta_impl(c, n_ctg, h_ctg_seg, h_seg, h_bytes, n_bytes, k, line_length, h_names, h_name_off, h_text, nullptr, text_cap, h_text_len);
-}
-
-int agc_hip_sample_fasta_dev(agc_hip_ctx *c, uint32_t n_ctg, const uint64_t *h_ctg_seg, const agc_hip_seg_src *h_seg, const uint8_t *h_bytes, uint64_t n_bytes, uint32_t k,
-                             uint32_t line_length, const char *h_names, const uint64_t *h_name_off, uint8_t *d_text, uint64_t text_cap, uint64_t *h_text_len)
-{
-    if (!c || !h_text_len || (n_ctg && (!h_ctg_seg || !h_name_off || (h_ctg_seg[n_ctg] && !h_seg) || (n_bytes && !h_bytes))) || (text_cap && !d_text))
-        return AGC_HIP_EINVAL;
-    return sample_fasta_impl(c, n_ctg, h_ctg_seg, h_seg, h_bytes, n_bytes, k, line_length, h_names, h_name_off, nullptr, d_text, text_cap, h_text_len);
 }
 
 // pinned host memory for the buffers results are copied into (a copy into pageable memory goes through a bounce buffer)
@@ -3270,100 +2999,8 @@ int agc_hip_zstd17_batch_dev(agc_hip_ctx *c, uint32_t n, const uint8_t *d_src, c
     return zstd17_batch_impl(c, n, nullptr, d_src ? d_src : (const uint8_t *)1, h_src_off, h_dst, dst_cap, h_dst_off);
 }
 
-// The decode (include/agc_hip.h) on the first stream.  The host reads every frame header: that sizes the output, and a frame whose
-// header is refused never reaches the decoder.  zstd_decode_kernel then gives every other frame a wave, its slice of the output and
-// its slice of the literals workspace (min(content size, 128 KiB): what a block's literals can need).
-// d_out: the caller's device buffer, or nullptr: the context's, copied to h_out.
-static int zstd_decode_impl(agc_hip_ctx *c, uint32_t n, const uint8_t *h_src, const uint64_t *h_src_off, uint8_t *h_out, uint8_t *d_out, uint64_t out_cap,
-                            uint64_t *h_out_off, uint32_t *h_status)
-{
-    for (uint32_t i = 0; i < n; ++i)
-        if (h_src_off[i + 1] < h_src_off[i]) {
-            c->err = "zstd_decode: frame " + std::to_string(i) + " ends in front of its start";
-            return AGC_HIP_EINVAL;
-        }
-    const uint64_t s0 = h_src_off[0], src_bytes = h_src_off[n] - s0;
-    std::vector<ZDecJob> jobs(n);
-    uint64_t tot = 0, ws_tot = 0;
-    uint32_t n_live = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint64_t len = h_src_off[i + 1] - h_src_off[i];
-        const zs::dec::FrameHeader h = zs::dec::parseFrameHeader(h_src + h_src_off[i], len);
-        const uint32_t ws_len = (std::min(h.contentSize, zs::BLOCKSIZE_MAX) + 15u) & ~15u;
-        jobs[i] = {h_src_off[i] - s0, tot, ws_tot, (uint32_t)len, h.contentSize, ws_len, h.status};
-        h_out_off[i] = tot;
-        tot += h.contentSize;
-        ws_tot += ws_len;
-        n_live += h.status == zs::dec::OK;
-        if (h_status)
-            h_status[i] = h.status;
-    }
-    h_out_off[n] = tot;
-    if (tot > out_cap) {
-        c->err = "zstd_decode: the output buffer holds " + std::to_string(out_cap) + " bytes, " + std::to_string(tot) + " are needed";
-        return AGC_HIP_ECAP;
-    }
-    std::vector<uint32_t> status(n);
-    if (n_live) {
-        HIPCHK(c, hipSetDevice(c->device));
-        CHK(ensure(c, c->d_zd_src, src_bytes + 64));
-        CHK(ensure(c, c->d_zd_jobs, (size_t)n * sizeof(ZDecJob)));
-        CHK(ensure(c, c->d_zd_status, (size_t)n * sizeof(uint32_t)));
-        CHK(ensure(c, c->d_zd_ws, ws_tot + 64));
-        if (!d_out) {
-            CHK(ensure(c, c->d_zd_out, tot + 64));
-            d_out = (uint8_t *)c->d_zd_out.p;
-        }
-        CHK(upload(c, c->d_zd_src.p, h_src + s0, src_bytes, c->stream));
-        CHK(upload(c, c->d_zd_jobs.p, jobs.data(), (size_t)n * sizeof(ZDecJob), c->stream));
-        {
-            KTimer t(c, AGC_HIP_K_ZSTD_DECODE);
-            hipLaunchKernelGGL(zstd_decode_kernel, dim3(n), dim3(WAVE), 0, c->stream, (const ZDecJob *)c->d_zd_jobs.p, n, (const uint8_t *)c->d_zd_src.p, d_out,
-                               (uint8_t *)c->d_zd_ws.p, (uint32_t *)c->d_zd_status.p); // a wave per frame
-        }
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(status.data(), c->d_zd_status.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        if (h_out && tot)
-            HIPCHK(c, hipMemcpyAsync(h_out, d_out, tot, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    } else
-        for (uint32_t i = 0; i < n; ++i)
-            status[i] = jobs[i].status;
-    for (uint32_t i = 0; i < n; ++i)
-        if (h_status)
-            h_status[i] = status[i];
-    for (uint32_t i = 0; i < n; ++i)
-        if (status[i] != zs::dec::OK) {
-            c->err = "zstd_decode: frame " + std::to_string(i) + " is refused: " + (status[i] == zs::dec::UNSUPPORTED ? "unsupported (status 1)" : "malformed (status 2)");
-            return AGC_HIP_EINVAL;
-        }
-    return AGC_HIP_OK;
-}
-
-int agc_hip_zstd_decode_batch(agc_hip_ctx *c, uint32_t n, const uint8_t *h_src, const uint64_t *h_src_off, uint8_t *h_out, uint64_t out_cap, uint64_t *h_out_off,
-                              uint32_t *h_status)
-{
-    if (!c || !h_out_off || (n && (!h_src_off || (h_src_off[n] > h_src_off[0] && !h_src))) || (out_cap && !h_out))
-        return AGC_HIP_EINVAL;
-    h_out_off[0] = 0;
-    if (!n)
-        return AGC_HIP_OK;
-    return zstd_decode_impl(c, n, h_src, h_src_off, h_out, nullptr, out_cap, h_out_off, h_status);
-}
-
-int agc_hip_zstd_decode_batch_dev(agc_hip_ctx *c, uint32_t n, const uint8_t *h_src, const uint64_t *h_src_off, uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_off,
-                                  uint32_t *h_status)
-{
-    if (!c || !h_out_off || (n && (!h_src_off || (h_src_off[n] > h_src_off[0] && !h_src))) || (out_cap && !d_out))
-        return AGC_HIP_EINVAL;
-    h_out_off[0] = 0;
-    if (!n)
-        return AGC_HIP_OK;
-    // (an output of 0 bytes: the context's buffer stands in for a d_out the caller did not have to give)
-    return zstd_decode_impl(c, n, h_src, h_src_off, nullptr, d_out, out_cap, h_out_off, h_status);
-}
-
 } // extern "C"
 
 #include "splitters.hip"
 #include "segments.hip"
+#include "read_api.hip"

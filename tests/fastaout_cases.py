@@ -8,7 +8,7 @@ A segment: {"kind": RAW / REF / DELTA, "rc", "stored": its symbols as the archiv
 segment that is not its contig's first are NOT the tail of the segment before (in an archive they are): a wrong skip shows."""
 import numpy as np
 
-from agc_amd import synth
+from agc_amd import capi, synth
 
 RAW, REF, DELTA = 0, 1, 2
 MML = 20
@@ -60,6 +60,36 @@ def expected_text(case):
     return b"".join(contig_text(n, contig_symbols(s, case["k"]), case["line_length"]) for n, s in case["contigs"])
 
 
+def contig_text_size(name_len, n_sym, line_length):
+    L = line_length or n_sym
+    return name_len + 2 + (n_sym + (n_sym + L - 1) // L if n_sym else 0)
+
+
+def plan_arrays(case, gid0, oracle):
+    """the case as agc_hip_sample_fasta takes it (the arguments of capi.Context.sample_fasta): reference i is group gid0 + i, the
+    deltas are the oracle's"""
+    lz = {}
+    segs, blob, ctg_seg, names, name_off, n_blob = [], [], [0], [], [0], 0
+    for name, ss in case["contigs"]:
+        for s in ss:
+            b = np.zeros(0, np.uint8)
+            if s["kind"] == RAW:
+                b = s["stored"]
+            elif s["kind"] == DELTA:
+                if s["ref"] not in lz:
+                    lz[s["ref"]] = oracle.LZ(case["refs"][s["ref"]], MML)
+                b = lz[s["ref"]].encode(s["stored"])
+                assert b.size or not s["stored"].size
+            segs.append((s["kind"], 0 if s["kind"] == RAW else gid0 + s["ref"], n_blob, b.size, s["stored"].size, s["rc"], 0))
+            blob.append(b)
+            n_blob += b.size
+        ctg_seg.append(len(segs))
+        names.append(name)
+        name_off.append(name_off[-1] + len(name))
+    return (np.array(ctg_seg, np.uint64), np.array(segs, capi.SEG_SRC_DTYPE), np.concatenate(blob + [np.zeros(0, np.uint8)]), case["k"], case["line_length"],
+            b"".join(names), np.array(name_off, np.uint64))
+
+
 def layout(case):
     """the arrays the text kernel reads, laid out here: the segments back to back, oriented, in `sym`"""
     k, ll = case["k"], case["line_length"]
@@ -80,8 +110,7 @@ def layout(case):
         ctg_seg.append(len(seg_start))
         names.append(name)
         name_off.append(name_off[-1] + len(name))
-        L = ll or pos
-        ctg_text.append(ctg_text[-1] + len(name) + 2 + (pos + (pos + L - 1) // L if pos else 0))
+        ctg_text.append(ctg_text[-1] + contig_text_size(len(name), pos, ll))
     u64 = lambda v: np.array(v, np.uint64)  # noqa: E731
     return {"ctg_text": u64(ctg_text), "ctg_seg": u64(ctg_seg), "ctg_sym": u64(ctg_sym), "name_off": u64(name_off), "names": b"".join(names),
             "seg_start": u64(seg_start), "seg_off": u64(seg_off), "skip": np.array(skip, np.uint32),

@@ -10,7 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 OUT = os.path.join(HERE, "_build")
 LIB = os.path.join(OUT, "libfastaout_host.so")
 SRC = os.path.join(HERE, "fastaout_host.cpp")
-DEPS = [SRC] + [os.path.join(ROOT, "agc_amd", "csrc", h) for h in ("fasta_out.h", "sym_view.h")]
+DEPS = [SRC] + [os.path.join(ROOT, "agc_amd", "csrc", h) for h in ("fasta_out.h", "fasta_plan.h", "sym_view.h")] + [os.path.join(ROOT, "include", "agc_hip.h")]
 
 
 def build(force=False):

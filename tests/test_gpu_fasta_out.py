@@ -34,26 +34,7 @@ def call_args(ctx, oracle, case):
     ctx.next_gid += len(case["refs"])
     for i, r in enumerate(case["refs"]):
         ctx.ref_register(gid0 + i, r, FC.MML)
-    lz = {}
-    segs, blob, ctg_seg, names, name_off, n_blob = [], [], [0], [], [0], 0
-    for name, ss in case["contigs"]:
-        for s in ss:
-            b = np.zeros(0, np.uint8)
-            if s["kind"] == FC.RAW:
-                b = s["stored"]
-            elif s["kind"] == FC.DELTA:
-                if s["ref"] not in lz:
-                    lz[s["ref"]] = oracle.LZ(case["refs"][s["ref"]], FC.MML)
-                b = lz[s["ref"]].encode(s["stored"])
-                assert b.size or not s["stored"].size
-            segs.append((s["kind"], 0 if s["kind"] == FC.RAW else gid0 + s["ref"], n_blob, b.size, s["stored"].size, s["rc"], 0))
-            blob.append(b)
-            n_blob += b.size
-        ctg_seg.append(len(segs))
-        names.append(name)
-        name_off.append(name_off[-1] + len(name))
-    return (np.array(ctg_seg, np.uint64), np.array(segs, capi.SEG_SRC_DTYPE), np.concatenate(blob + [np.zeros(0, np.uint8)]), case["k"], case["line_length"],
-            b"".join(names), np.array(name_off, np.uint64))
+    return FC.plan_arrays(case, gid0, oracle)
 
 
 def run_case(ctx, oracle, case):
