@@ -1,12 +1,13 @@
 // api.hip -- the C ABI of include/agc_hip.h: context, HBM arenas, kernel launches.
 // Host-side logic here is orchestration only (buffer management, sorting sparse hit
-// lists, sizing tables with the reference's double arithmetic); all symbol-level work is
-// done by the kernels in scan_kernels.hip / lz_kernels.hip.  There is no CPU fallback.
+// lists; the LZ write path's arithmetic -- batch order, offsets, the chunk plan, a reference's layout -- is lz_plan.h); all
+// symbol-level work is done by the kernels in scan_kernels.hip / lz_kernels.hip.  There is no CPU fallback.
 // This file: the context, the helpers every entry point shares (ensure, upload, KTimer, ...) and the create path.  The read path
 // (LZ decode, a sample's FASTA text, zstd decode) is read_api.hip, included at the end with splitters.hip and segments.hip: the
 // library stays one translation unit.
 #include "../../include/agc_hip.h"
 #include "dev_common.h"
+#include "lz_plan.h"
 
 #include <algorithm>
 #include <atomic>
@@ -157,8 +158,7 @@ struct agc_hip_ctx {
         void *segs = nullptr, *counts = nullptr, *d_ctg_off = nullptr;
         void *flag = nullptr, *capv = nullptr, *known_rank = nullptr, *cap_off = nullptr, *descs = nullptr, *lcnt = nullptr;
     } seg_state;
-    DevBuf d_ranges, d_hits, d_counter, d_segs, d_slices, d_scratch, d_resv, d_resp, d_dstoff, d_compact,
-        d_jobs, d_counts, d_in, d_pp_cnt, d_pp_off, d_pp_total, d_lag, d_sample, d_zsrc, d_zdst, d_zws, d_zjobs, d_zsize, d_zout, d_zdstoff, d_maybe, d_fjobs;
+    DevBuf d_ranges, d_hits, d_counter, d_slices, d_jobs, d_counts, d_in, d_pp_cnt, d_pp_off, d_pp_total, d_lag, d_sample, d_zsrc, d_zdst, d_zws, d_zjobs, d_zsize, d_zout, d_zdstoff, d_maybe, d_fjobs;
     struct ReadBufs { // the read path (read_api.hip)
         DevBuf d_dec_enc, d_dec_jobs, d_dec_res, d_dec_out; // agc_hip_lz_decode_batch*: the deltas, their descriptors, lengths + status, the symbols
         DevBuf d_fa_sym, d_fa_copy, d_fa_plan, d_fa_text;   // agc_hip_sample_fasta*: the sample's symbols, the copy jobs, the text plan, the text
@@ -184,10 +184,25 @@ struct agc_hip_ctx {
         int n_recorded = 0; // events recorded when it left
     } up_part[UP_PARTS];
 
-    // second LZ lane: agc_hip_lz_encode_begin_dev / _end run the encode of a whole sample on the lane's stream with their own scratch,
-    // beside the estimates / cost vectors / index builds the caller goes on with on `stream`
-    struct Lane2 {
-        DevBuf d_segs, d_counter, d_resv, d_resp, d_scratch, d_dstoff, d_compact;
+    // An LZ parse stream: a stream, the parse's buffers and the chunk buffers of a parse in chunks.  lane(0) is the steps' stream (the
+    // estimates, cost vectors, one-call encodes; other entry points of that stream share d_scratch, d_dstoff and d_compact with the
+    // parse); lane(1) and lane(2) are the encode lanes: agc_hip_lz_encode_begin_* / _end run the encode of a whole sample on the
+    // lane's stream with their own scratch, beside what the caller goes on with on `stream`.  lane(2): a second encode in flight --
+    // the segments of a sample whose group was minted by that very sample, launched at commit time behind the whole-sample encode
+    // of lane(1) and collected by the same bookkeeping task
+    struct LzLane {
+        hipStream_t s = nullptr; // lane 0: the context's `stream`; an encode lane: `own`, at the first stream's priority
+        Stream own;
+        DevBuf d_segs, d_resv, d_resp, d_scratch, d_dstoff, d_compact;
+        struct Chunks { // launch_parse: chunk list, logs and per-chunk output
+            DevBuf d_jobs, d_seg0, d_logs, d_logn, d_out;
+            // the chunk logs of a human-size batch are 0.7 GB: a launch of thousands of parses that is NOT parsed in chunks has a helper
+            // thread allocate them, so that the first batch that is -- one text of a few hundred kb among 3 000, twice in twenty samples --
+            // does not pay a hipMalloc inside a step (27-41 ms on a box whose VRAM the process touches for the first time)
+            std::future<DevBuf> logs_ahead;
+            bool logs_asked = false;
+        } chunks;
+        // ---- the encode lanes only
         DevBuf d_n; // the lane's own copy of a segment count made on the device (the work area it came from is re-laid-out by the next sample)
         PackTemp pk;
         PinnedBuf h_lens; // (a device-to-host copy into pageable memory would make begin wait for the kernel)
@@ -200,10 +215,8 @@ struct agc_hip_ctx {
         // the parse reads -- the sample staging buffers -- waits for the event on its own stream (sample_buffer, prefetch)
         Event done;
         bool done_valid = false;
-        Stream s; // the lane's stream, at the first stream's priority
-    } l2, l3; // (l3: a second encode in flight -- the segments of a sample whose group was minted by that very sample, launched at
-              // commit time behind the whole-sample encode of l2 and collected by the same bookkeeping task)
-    Lane2 &lane(int which) { return which == 2 ? l3 : l2; }
+    } lanes[3];
+    LzLane &lane(int which) { return lanes[which]; }
 
     // the NEXT sample, started ahead of its turn (agc_hip_prefetch_packed_dev): expansion into one of two staging buffers and the
     // packed splitter scan, on a stream of their own with their own scratch -- they fill the gaps the sample in front leaves on the
@@ -232,16 +245,6 @@ struct agc_hip_ctx {
         bool pending = false, timed = false;
         Event e0, e1;
     } pfa;
-
-    // the parse in chunks (launch_parse): chunk list, logs and per-chunk output of the first stream and of the two encode lanes
-    struct ChunkBufs {
-        DevBuf d_jobs, d_seg0, d_logs, d_logn, d_out;
-        // the chunk logs of a human-size batch are 0.7 GB: a launch of thousands of parses that is NOT parsed in chunks has a helper
-        // thread allocate them, so that the first batch that is -- one text of a few hundred kb among 3 000, twice in twenty samples --
-        // does not pay a hipMalloc inside a step (27-41 ms on a box whose VRAM the process touches for the first time)
-        std::future<DevBuf> logs_ahead;
-        bool logs_asked = false;
-    } chunk_bufs[3];
 
     // pinned host allocations handed out by agc_hip_host_alloc
     std::vector<PinnedBuf> host_allocs;
@@ -536,10 +539,12 @@ bool make_entropy_lane(agc_hip_ctx *c)
 
 // An encode lane, at the first stream's priority: measured with a low-priority lane the whole-sample encode is starved by the
 // classification kernels until they are done and ends up on the critical path of the NEXT sample's launch
-bool make_encode_lane(agc_hip_ctx::Lane2 &L)
+bool make_encode_lane(agc_hip_ctx::LzLane &L)
 {
-    return hipStreamCreateWithFlags(&L.s.h, hipStreamNonBlocking) == hipSuccess && hipEventCreate(&L.e0.h) == hipSuccess && hipEventCreate(&L.e1.h) == hipSuccess &&
-           hipEventCreateWithFlags(&L.ready.h, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&L.done.h, hipEventDisableTiming) == hipSuccess;
+    const bool ok = hipStreamCreateWithFlags(&L.own.h, hipStreamNonBlocking) == hipSuccess && hipEventCreate(&L.e0.h) == hipSuccess && hipEventCreate(&L.e1.h) == hipSuccess &&
+                    hipEventCreateWithFlags(&L.ready.h, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&L.done.h, hipEventDisableTiming) == hipSuccess;
+    L.s = L.own;
+    return ok;
 }
 
 int upload_refs(agc_hip_ctx *c)
@@ -554,7 +559,7 @@ int upload_refs(agc_hip_ctx *c)
     size_t lo = c->refs_dirty_lo, hi = std::min(c->refs_dirty_hi, c->refs.size());
     const size_t need = std::max<size_t>(1, c->refs.size()) * sizeof(RefDesc);
     if (need > c->d_refs.cap || c->refs_on_dev == 0) {
-        for (auto *ln : {&c->l2, &c->l3})
+        for (auto *ln : {&c->lane(1), &c->lane(2)})
             if (ln->pending)
                 HIPCHK(c, hipStreamSynchronize(ln->s)); // the encode in flight reads the buffer that is about to be freed
         CHK(ensure(c, c->d_refs, need));
@@ -665,7 +670,7 @@ bool slices_inside(const PackedSrc &src, uint32_t n, const uint64_t *h_off, cons
 struct SliceBufs {
     DevBuf &slices, &out, &lag;
 };
-SliceBufs slice_bufs(agc_hip_ctx *c) { return {c->d_slices, c->d_compact, c->d_lag}; }
+SliceBufs slice_bufs(agc_hip_ctx *c) { return {c->d_slices, c->lane(0).d_compact, c->d_lag}; }
 SliceBufs slice_bufs(agc_hip_ctx::RefStore &r) { return {r.d_slices, r.d_out, r.d_lag}; }
 
 // the jobs of n slices of `src` in b.slices: slice i goes to b.out + h_out_off[i] (h_out_off[n] bytes in all), or nowhere when
@@ -740,10 +745,11 @@ int agc_hip_create(agc_hip_ctx **out, int device)
     agc_hip_ctx *c = new agc_hip_ctx();
     c->device = device;
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream.h, hipStreamNonBlocking) != hipSuccess || !make_entropy_lane(c) ||
-        !make_encode_lane(c->l2) || !make_encode_lane(c->l3) || hipEventCreate(&c->zev0.h) != hipSuccess || hipEventCreate(&c->zev1.h) != hipSuccess) {
+        !make_encode_lane(c->lane(1)) || !make_encode_lane(c->lane(2)) || hipEventCreate(&c->zev0.h) != hipSuccess || hipEventCreate(&c->zev1.h) != hipSuccess) {
         delete c; // (releases what was made)
         return AGC_HIP_ENODEV;
     }
+    c->lane(0).s = c->stream;
     *out = c;
     return AGC_HIP_OK;
 }
@@ -756,14 +762,14 @@ void agc_hip_destroy(agc_hip_ctx *c)
     // Every stream the context has made runs dry and both helper threads hand over what they allocated BEFORE the first member
     // goes: nothing on the device or on a thread refers to a member any more, so the order in which the members' destructors run
     // does not matter.
-    for (hipStream_t s_ : {c->stream.h, c->zstream.h, c->zstream2.h, c->l2.s.h, c->l3.s.h, c->pfa.stream.h, c->pf.stream.h, c->ref_store_stream.h})
+    for (hipStream_t s_ : {c->stream.h, c->zstream.h, c->zstream2.h, c->lane(1).s, c->lane(2).s, c->pfa.stream.h, c->pf.stream.h, c->ref_store_stream.h})
         if (s_)
             (void)hipStreamSynchronize(s_);
     if (c->arena_spare.valid())
         (void)c->arena_spare.get();
-    for (auto &cb : c->chunk_bufs)
-        if (cb.logs_ahead.valid())
-            (void)cb.logs_ahead.get();
+    for (auto &L : c->lanes)
+        if (L.chunks.logs_ahead.valid())
+            (void)L.chunks.logs_ahead.get();
     delete c;
 }
 
@@ -814,8 +820,8 @@ int agc_hip_sample_buffer(agc_hip_ctx *c, uint64_t bytes, uint8_t **d_ptr)
     if (!c || !d_ptr)
         return AGC_HIP_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
-    // (the encode of the previous sample may still be reading the buffer on the second lane: see Lane2::done)
-    for (auto *ln : {&c->l2, &c->l3})
+    // (the encode of the previous sample may still be reading the buffer on the second lane: see LzLane::done)
+    for (auto *ln : {&c->lane(1), &c->lane(2)})
         if (ln->done_valid) {
             if (bytes + 4096 > c->d_sample.cap)
                 HIPCHK(c, hipEventSynchronize(ln->done)); // the buffer is about to be replaced
@@ -847,9 +853,9 @@ int agc_hip_sample_pack(agc_hip_ctx *c, const uint8_t *d_codes, uint64_t n_symbo
     if (!c || !out || (n_symbols && !d_codes))
         return AGC_HIP_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
-    // (the encode of the previous sample may still be reading these buffers on the second lane: see Lane2::done; and the copy of
+    // (the encode of the previous sample may still be reading these buffers on the second lane: see LzLane::done; and the copy of
     // its new references on the reference-store stream)
-    for (auto *ln : {&c->l2, &c->l3})
+    for (auto *ln : {&c->lane(1), &c->lane(2)})
         if (ln->done_valid)
             HIPCHK(c, hipEventSynchronize(ln->done));
     for (auto &rs : c->ref_store)
@@ -1333,9 +1339,9 @@ int agc_hip_sample_pack_fasta(agc_hip_ctx *c, uint32_t n_ctg, const uint8_t *con
         h_ctg_off[i] = 0;
     if (!tot)
         return AGC_HIP_OK;
-    // (the encode of the previous sample may still be reading the packed buffers on a lane: see Lane2::done; and the copy of its new
+    // (the encode of the previous sample may still be reading the packed buffers on a lane: see LzLane::done; and the copy of its new
     // references on the reference-store stream)
-    for (auto *ln : {&c->l2, &c->l3})
+    for (auto *ln : {&c->lane(1), &c->lane(2)})
         if (ln->done_valid)
             HIPCHK(c, hipEventSynchronize(ln->done));
     for (auto &rs : c->ref_store)
@@ -1622,42 +1628,31 @@ static int ref_register_impl(agc_hip_ctx *c, uint32_t n_refs, const uint32_t *h_
             return AGC_HIP_EINVAL;
     }
 
-    // 1. stored form: ref_size symbols in 2-bit words + REF_TAIL_WORDS words of slack, 16-byte aligned
+    // 1. the stored forms, back to back (lz_plan.h: stored_bytes)
     std::vector<IdxBuild> jobs(n_refs);
-    size_t ref_bytes = 0;
-    std::vector<size_t> roff(n_refs);
+    std::vector<uint64_t> roff(n_refs), toff(n_refs), boff(n_refs);
+    uint8_t *rbase = nullptr, *tbase = nullptr, *bbase = nullptr;
+    CHK(arena_alloc(c, lp::prefix(n_refs, roff.data(), [&](uint32_t i) { return lp::stored_bytes(h_len[i]); }), &rbase));
     for (uint32_t i = 0; i < n_refs; ++i) {
-        roff[i] = ref_bytes;
-        ref_bytes += ((((size_t)h_len[i] + 15) / 16 + REF_TAIL_WORDS) * 4 + 15) & ~(size_t)15;
-    }
-    uint8_t *rbase = nullptr;
-    CHK(arena_alloc(c, ref_bytes, &rbase));
-    for (uint32_t i = 0; i < n_refs; ++i) {
-        jobs[i].src = {src.words, src.esc_index, src.esc_bytes, h_off[i], h_len[i], h_rc ? (uint32_t)(h_rc[i] != 0) : 0u};
-        jobs[i].words = (uint32_t *)(rbase + roff[i]);
-        jobs[i].esc_index = nullptr;
-        jobs[i].esc_bytes = nullptr;
-        jobs[i].table = nullptr;
-        jobs[i].bloom = nullptr;
-        jobs[i].ref_size = h_len[i];
-        jobs[i].key_len = key_len;
-        jobs[i].ht_mask = 0;
-        jobs[i].is_short = (h_len[i] / HASHING_STEP) < 65535u; // lz_diff.cpp:146
+        IdxBuild &j = jobs[i] = IdxBuild(); // (escape blocks, table and filter: null until step 2 places them)
+        j.src = {src.words, src.esc_index, src.esc_bytes, h_off[i], h_len[i], h_rc ? (uint32_t)(h_rc[i] != 0) : 0u};
+        j.words = (uint32_t *)(rbase + roff[i]);
+        j.ref_size = h_len[i];
+        j.key_len = key_len;
+        j.is_short = lp::is_short(h_len[i]);
     }
     CHK(ensure(c, c->d_jobs, (size_t)n_refs * sizeof(IdxBuild)));
     CHK(ensure(c, c->d_counts, (size_t)n_refs * 4));
     CHK(ensure(c, c->d_flags, (size_t)n_refs * 4));
     CHK(upload(c, c->d_jobs.p, jobs.data(), (size_t)n_refs * sizeof(IdxBuild), c->stream));
-    // few references per batch (steady state): spread each over several blocks to fill the chip
-    const uint32_t split = n_refs >= 2048 ? 1u : std::min<uint32_t>(16u, 2048u / n_refs);
+    const uint32_t split = lp::split_factor(n_refs);
     HIPCHK(c, hipMemsetAsync(c->d_flags.p, 0, (size_t)n_refs * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_counts.p, 0, (size_t)n_refs * 4, c->stream));
     {
         KTimer t(c, AGC_HIP_K_REFSTORE);
         hipLaunchKernelGGL(ref_pack_kernel, dim3(n_refs * split), dim3(256), 0, c->stream, (const IdxBuild *)c->d_jobs.p, (uint32_t *)c->d_flags.p, split);
     }
-    // 2. count keys -> table sizes (prepare_index, lz_diff.cpp:81-125: double division by 0.7,
-    //    round down to a power of two, double it, at least 8)
+    // 2. count keys -> table sizes (lz_plan.h: ht_size), tables pre-set to all ones
     std::vector<uint32_t> counts(n_refs), flags(n_refs);
     {
         KTimer t(c, AGC_HIP_K_INDEX);
@@ -1668,46 +1663,26 @@ static int ref_register_impl(agc_hip_ctx *c, uint32_t n_refs, const uint32_t *h_
     HIPCHK(c, hipMemcpyAsync(counts.data(), c->d_counts.p, (size_t)n_refs * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(flags.data(), c->d_flags.p, (size_t)n_refs * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    size_t tab_bytes = 0;
-    std::vector<size_t> toff(n_refs);
-    for (uint32_t i = 0; i < n_refs; ++i) {
-        uint64_t hs = (uint64_t)((double)counts[i] / 0.7);
-        while (hs & (hs - 1))
-            hs &= hs - 1;
-        hs <<= 1;
-        if (hs < 8)
-            hs = 8;
-        jobs[i].ht_mask = (uint32_t)(hs - 1);
-        toff[i] = tab_bytes;
-        tab_bytes += (size_t)hs * (jobs[i].is_short ? 4 : 8);
-        tab_bytes = (tab_bytes + 255) & ~(size_t)255;
-    }
-    uint8_t *tbase = nullptr;
+    const uint64_t tab_bytes = lp::prefix(n_refs, toff.data(), [&](uint32_t i) { return lp::table_bytes(h_len[i], counts[i]); });
     CHK(arena_alloc(c, tab_bytes, &tbase));
     HIPCHK(c, hipMemsetAsync(tbase, 0xFF, tab_bytes, c->stream));
     // key filters (two per reference, sized by its length: dev_common.h; zeroed; the insert kernel sets the bits)
-    uint8_t *bbase = nullptr;
-    std::vector<size_t> boff(n_refs);
-    size_t bloom_bytes = 0;
-    for (uint32_t i = 0; i < n_refs; ++i) {
-        boff[i] = bloom_bytes;
-        bloom_bytes += (size_t)2 * key_bloom_half_words(key_bloom_shift(jobs[i].ref_size)) * 8;
-    }
+    const uint64_t bloom_bytes = lp::prefix(n_refs, boff.data(), [&](uint32_t i) { return lp::filter_bytes(h_len[i]); });
     CHK(arena_alloc(c, bloom_bytes, &bbase));
     HIPCHK(c, hipMemsetAsync(bbase, 0, bloom_bytes, c->stream));
     // references that hold a symbol outside ACGT: escape index + one byte per symbol for the blocks that need it
     std::vector<EscJob> ejobs;
     for (uint32_t i = 0; i < n_refs; ++i) {
+        jobs[i].ht_mask = (uint32_t)(lp::ht_size(counts[i]) - 1);
         jobs[i].table = tbase + toff[i];
         jobs[i].bloom = (unsigned long long *)(bbase + boff[i]);
         if (flags[i]) {
-            const uint32_t nb = (h_len[i] + PACK_BLOCK - 1) / PACK_BLOCK;
+            const uint32_t nb = lp::esc_blocks(h_len[i]);
             uint8_t *eb = nullptr;
-            CHK(arena_alloc(c, (size_t)nb * 4 + 64 + (size_t)nb * PACK_BLOCK, &eb));
+            CHK(arena_alloc(c, lp::esc_alloc_bytes(nb), &eb));
             jobs[i].esc_index = (int32_t *)eb;
-            jobs[i].esc_bytes = eb + (((size_t)nb * 4 + 64 + 15) & ~(size_t)15);
-            for (uint32_t b = 0; b < nb; ++b)
-                ejobs.push_back({jobs[i].src, jobs[i].esc_index, jobs[i].esc_bytes, b, 0u});
+            jobs[i].esc_bytes = eb + lp::esc_bytes_at(nb);
+            lp::push_esc_jobs(ejobs, jobs[i].src, jobs[i].esc_index, jobs[i].esc_bytes);
         }
     }
     if (!ejobs.empty()) {
@@ -1742,20 +1717,8 @@ static int ref_register_impl(agc_hip_ctx *c, uint32_t n_refs, const uint32_t *h_
         r.is_short = jobs[i].is_short;
         r.valid = 1;
     }
-    {
-        uint32_t min_gid = max_gid;
-        for (uint32_t i = 0; i < n_refs; ++i)
-            min_gid = std::min(min_gid, h_gid[i]);
-        if (!c->refs_dirty || c->refs_dirty_hi <= c->refs_dirty_lo) {
-            c->refs_dirty_lo = min_gid;
-            c->refs_dirty_hi = (size_t)max_gid + 1;
-        } else {
-            c->refs_dirty_lo = std::min<size_t>(c->refs_dirty_lo, min_gid);
-            c->refs_dirty_hi = std::max<size_t>(c->refs_dirty_hi, (size_t)max_gid + 1);
-        }
-        // (descriptors the resize above added between the old end and min_gid are invalid ones: they go over too)
-        c->refs_dirty_lo = std::min(c->refs_dirty_lo, c->refs_on_dev);
-    }
+    const lp::DirtyRange dr = lp::widen_dirty(c->refs_dirty, {c->refs_dirty_lo, c->refs_dirty_hi}, c->refs_on_dev, *std::min_element(h_gid, h_gid + n_refs), max_gid);
+    c->refs_dirty_lo = dr.lo, c->refs_dirty_hi = dr.hi;
     c->refs_dirty = true;
     return AGC_HIP_OK;
 }
@@ -1858,20 +1821,19 @@ int agc_hip_ref_index_get(agc_hip_ctx *c, uint32_t gid, uint32_t *h_table, uint6
 
 namespace {
 
+using LzLane = agc_hip_ctx::LzLane;
+
 struct Batch {
-    std::vector<SegDesc> segs; // processing order (longest first); SegDesc.pad = original index
-    uint64_t out_total = 0;    // scratch units (bytes or u32s)
+    std::vector<SegDesc> segs; // processing order (longest first); SegDesc.idx = original index
+    uint64_t out_total = 0;    // scratch units (bytes or cost_t)
+    uint64_t text_total = 0;   // symbols of all texts
 };
 
-// Builds descriptors: every text is a view into the packed buffer (either orientation -- nothing is copied or staged).
-int prepare_batch(agc_hip_ctx *c, int mode, uint32_t n, const uint32_t *h_gid, const PackedSrc &src, const uint64_t *h_off,
-                  const uint32_t *h_len, const uint8_t *h_rc, const uint8_t *h_prefix, Batch &b, int lane = 0)
+// Builds the descriptors of a parse on lane L: every text is a view into the packed buffer (either orientation -- nothing is copied or
+// staged).  (An encode lane: encode only -- no filter bitmaps.)
+int prepare_batch(agc_hip_ctx *c, LzLane &L, int mode, uint32_t n, const uint32_t *h_gid, const PackedSrc &src, const uint64_t *h_off, const uint32_t *h_len,
+                  const uint8_t *h_rc, const uint8_t *h_prefix, Batch &b)
 {
-    // (lane 2: encode only -- no filter bitmaps; its own scratch and stream)
-    // (lane: 0 = the first stream and its buffers; 1, 2 = an encode lane of its own, agc_hip_ctx::lane)
-    DevBuf &L_segs = lane ? c->lane(lane).d_segs : c->d_segs, &L_counter = lane ? c->lane(lane).d_counter : c->d_counter,
-           &L_resv = lane ? c->lane(lane).d_resv : c->d_resv, &L_resp = lane ? c->lane(lane).d_resp : c->d_resp;
-    const hipStream_t L_stream = lane ? c->lane(lane).s : c->stream;
     Laps LAP("prepare_batch", n);
     for (uint32_t i = 0; i < n; ++i)
         if (h_gid[i] >= c->refs.size() || !c->refs[h_gid[i]].valid) {
@@ -1884,262 +1846,195 @@ int prepare_batch(agc_hip_ctx *c, int mode, uint32_t n, const uint32_t *h_gid, c
     }
     LAP("valid");
     CHK(upload_refs(c));
-    // longest first, stable in the index: LSD radix sort on ~len (3 passes of 11 bits; a comparison sort of the 50 k segments
-    // of a human sample costs milliseconds of host time per call)
-    std::vector<uint32_t> order(n);
-    {
-        std::vector<uint32_t> tmp(n);
-        for (uint32_t i = 0; i < n; ++i)
-            order[i] = i;
-        uint32_t *src = order.data(), *dst = tmp.data();
-        for (int pass = 0; pass < 3; ++pass) {
-            const int sh = 11 * pass;
-            uint32_t cnt[2049] = {0};
-            for (uint32_t i = 0; i < n; ++i)
-                ++cnt[((~h_len[src[i]] >> sh) & 2047u) + 1];
-            for (int t = 0; t < 2048; ++t)
-                cnt[t + 1] += cnt[t];
-            for (uint32_t i = 0; i < n; ++i)
-                dst[cnt[(~h_len[src[i]] >> sh) & 2047u]++] = src[i];
-            std::swap(src, dst);
-        }
-        if (src != order.data())
-            std::memcpy(order.data(), src, (size_t)n * 4);
-    }
+    const std::vector<uint32_t> order = lp::longest_first(n, h_len);
     LAP("sort");
-    if (Laps::enabled() && mode == MODE_COSTVEC && n) {
-        uint64_t tot = 0;
-        for (uint32_t i = 0; i < n; ++i)
-            tot += h_len[i];
-        fprintf(stderr, "    cost-vector batch: %u parses, %.1f Mb of text, longest %u %u %u %u, median %u\n", n, tot / 1e6, h_len[order[0]], h_len[order[n > 1 ? 1 : 0]],
-                h_len[order[n > 2 ? 2 : 0]], h_len[order[n > 3 ? 3 : 0]], h_len[order[n / 2]]);
-    }
-    std::vector<uint64_t> ooff(n);
-    uint64_t tot = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        ooff[i] = tot;
-        if (mode == MODE_ENCODE)
-            tot += (((uint64_t)h_len[i] + 5ULL * h_len[i] / 16 + 64) + 15) & ~15ULL; // a >=16-symbol match costs <= 21 bytes
-        else if (mode == MODE_COSTVEC)
-            tot += h_len[i];
-    }
-    b.out_total = tot;
-    b.segs.resize(n);
+    b.text_total = std::accumulate(h_len, h_len + n, (uint64_t)0);
+    if (Laps::enabled() && mode == MODE_COSTVEC && n)
+        fprintf(stderr, "    cost-vector batch: %u parses, %.1f Mb of text, longest %u %u %u %u, median %u\n", n, b.text_total / 1e6, h_len[order[0]],
+                h_len[order[n > 1 ? 1 : 0]], h_len[order[n > 2 ? 2 : 0]], h_len[order[n > 3 ? 3 : 0]], h_len[order[n / 2]]);
+    std::vector<uint64_t> ooff(n), moff(n, 0);
+    b.out_total = lp::out_offsets(mode, n, h_len, ooff.data());
     // estimate / cost vector: one "may match" bit per text position (key_filter_kernel) lets the parse skip literal runs
+    if (mode != MODE_ENCODE)
+        CHK(ensure(c, c->d_maybe, lp::filter_word_offsets(n, h_len, moff.data()) * 8 + 64));
     std::vector<FilterJob> fjobs;
-    std::vector<uint64_t> moff(n, 0);
-    if (mode != MODE_ENCODE) {
-        uint64_t words = 0;
-        for (uint32_t i = 0; i < n; ++i) {
-            moff[i] = words;
-            words += ((uint64_t)h_len[i] + 63) / 64 + 1;
-        }
-        CHK(ensure(c, c->d_maybe, words * 8 + 64));
-    }
+    b.segs.resize(n);
     for (uint32_t p = 0; p < n; ++p) {
         const uint32_t i = order[p];
         SegDesc &s = b.segs[p];
-        s.maybe = nullptr;
+        s = SegDesc();
         s.text = {src.words, src.esc_index, src.esc_bytes, h_off[i], h_len[i], (h_rc && h_rc[i]) ? 1u : 0u};
         s.out_off = ooff[i];
         s.ref_slot = h_gid[i];
         s.flags = (h_prefix && h_prefix[i]) ? 1u : 0u;
         s.idx = i;
-        s.pad = 0;
         const RefDesc &rd = c->refs[h_gid[i]];
         if (mode != MODE_ENCODE && rd.bloom && h_len[i] > 4 * WAVE) { // (short texts: not worth a block)
-            s.maybe = (const unsigned long long *)c->d_maybe.p + moff[i];
-            for (uint32_t ch = 0; ch < h_len[i]; ch += FILTER_CHUNK)
-                fjobs.push_back({s.text, rd.bloom, (unsigned long long *)c->d_maybe.p + moff[i], rd.key_len, ch, key_bloom_shift(rd.ref_size), 0u});
+            unsigned long long *maybe = (unsigned long long *)c->d_maybe.p + moff[i];
+            s.maybe = maybe;
+            lp::push_filter_jobs(fjobs, s.text, rd.bloom, maybe, rd.key_len, rd.ref_size);
         }
     }
     if (!fjobs.empty()) {
         CHK(ensure(c, c->d_fjobs, fjobs.size() * sizeof(FilterJob)));
-        CHK(upload(c, c->d_fjobs.p, fjobs.data(), fjobs.size() * sizeof(FilterJob), L_stream));
+        CHK(upload(c, c->d_fjobs.p, fjobs.data(), fjobs.size() * sizeof(FilterJob), L.s));
         {
             KTimer t(c, AGC_HIP_K_FILTER);
-            hipLaunchKernelGGL(key_filter_kernel, dim3((uint32_t)fjobs.size()), dim3(FILTER_THREADS), 0, L_stream, (const FilterJob *)c->d_fjobs.p);
+            hipLaunchKernelGGL(key_filter_kernel, dim3((uint32_t)fjobs.size()), dim3(FILTER_THREADS), 0, L.s, (const FilterJob *)c->d_fjobs.p);
         }
         HIPCHK(c, hipGetLastError());
     }
     LAP("descriptors");
-    CHK(ensure(c, L_segs, (size_t)n * sizeof(SegDesc), L_stream));
-    CHK(upload(c, L_segs.p, b.segs.data(), (size_t)n * sizeof(SegDesc), L_stream));
-    CHK(ensure(c, L_counter, 64, L_stream));
-    HIPCHK(c, hipMemsetAsync(L_counter.p, 0, 4, L_stream));
-    CHK(ensure(c, L_resv, (size_t)n * 4, L_stream));
-    CHK(ensure(c, L_resp, (size_t)n * 4, L_stream));
+    CHK(ensure(c, L.d_segs, (size_t)n * sizeof(SegDesc), L.s));
+    CHK(upload(c, L.d_segs.p, b.segs.data(), (size_t)n * sizeof(SegDesc), L.s));
+    CHK(ensure(c, L.d_resv, (size_t)n * 4, L.s));
+    CHK(ensure(c, L.d_resp, (size_t)n * 4, L.s));
     LAP("upload");
     return AGC_HIP_OK;
 }
 
-// A launch with few, long texts is a handful of dependent chains on an empty GPU: such batches are parsed in chunks (lz_kernels.hip:
-// ChunkCtl) -- a wavefront per 4096-symbol chunk, then a wavefront per text that joins them.  AGC_HIP_LZ_CHUNK=<symbols> forces a chunk
-// length for every launch the host has descriptors of (the tests run the whole LZ suite that way), 0 switches the path off.
-template <int MODE>
-int launch_parse(agc_hip_ctx *c, uint32_t n, uint8_t *out_bytes, uint32_t *out_u32, int lane = 0, const uint32_t *n_dev = nullptr, const Batch *b = nullptr)
+// The chunk list of a launch in chunks of chunk_len, its logs and (encode) its per-chunk output in the lane's chunk buffers -> pl;
+// pl.n_jobs stays 0 when there would be too many chunks (lz_plan.h): the launch then parses whole texts
+int place_chunks(agc_hip_ctx *c, LzLane &L, const Batch &b, uint32_t chunk_len, bool encode, ChunkPlan &pl)
 {
-    const uint32_t grid = (n + 3) / 4; // one wave per segment, 4 waves per block
-    const hipStream_t st = lane ? c->lane(lane).s : c->stream;
-    const RefDesc *d_refs = (const RefDesc *)c->d_refs.p;
-    const SegDesc *d_segs = (const SegDesc *)(lane ? c->lane(lane).d_segs.p : c->d_segs.p);
-    uint32_t *d_resv = (uint32_t *)(lane ? c->lane(lane).d_resv.p : c->d_resv.p), *d_resp = (uint32_t *)(lane ? c->lane(lane).d_resp.p : c->d_resp.p);
-    static const int forced = getenv("AGC_HIP_LZ_CHUNK") ? atoi(getenv("AGC_HIP_LZ_CHUNK")) : -1;
-    uint32_t chunk_len = 0;
-    if (b && !n_dev && n && forced != 0 && b->segs.size() == n) {
-        if (forced > 0)
-            chunk_len = (uint32_t)std::max(64, forced);
-        else if (b->segs[0].text.len >= 16384) { // (longest first)
-            // worth it when the longest text's chain outlasts the launch's work spread over the chip (~6 k wavefronts in flight):
-            // the diverged collections' few long texts, not the 3 000 cost-vector parses of a human sample
-            uint64_t total = 0;
-            for (const SegDesc &sd : b->segs)
-                total += sd.text.len;
-            if ((uint64_t)b->segs[0].text.len * 6144 > 4 * total)
-                chunk_len = 4096;
+    std::vector<ChunkJob> jobs;
+    std::vector<uint32_t> seg0;
+    if (!lp::plan_chunks(b.segs.data(), (uint32_t)b.segs.size(), chunk_len, encode, jobs, seg0, pl))
+        return AGC_HIP_OK;
+    LzLane::Chunks &cb = L.chunks;
+    CHK(ensure(c, cb.d_jobs, jobs.size() * sizeof(ChunkJob), L.s));
+    CHK(ensure(c, cb.d_seg0, seg0.size() * 4, L.s));
+    if (cb.logs_ahead.valid()) { // (allocated ahead by a helper thread: see LzLane::Chunks)
+        DevBuf ahead = cb.logs_ahead.get();
+        if (ahead.p && ahead.cap > cb.d_logs.cap) { // (otherwise it goes back as `ahead` goes)
+            if (cb.d_logs.p)
+                HIPCHK(c, hipStreamSynchronize(L.s));
+            cb.d_logs = std::move(ahead);
         }
     }
-    if (chunk_len) {
-        agc_hip_ctx::ChunkBufs &cb = c->chunk_bufs[lane];
-        std::vector<ChunkJob> jobs;
-        std::vector<uint32_t> seg0(n + 1);
-        for (uint32_t i = 0; i < n; ++i) {
-            seg0[i] = (uint32_t)jobs.size();
-            const uint32_t len = (uint32_t)b->segs[i].text.len, nc = std::max<uint32_t>(1, (len + chunk_len - 1) / chunk_len);
-            for (uint32_t ch = 0; ch < nc; ++ch)
-                jobs.push_back({i, ch});
-        }
-        seg0[n] = (uint32_t)jobs.size();
-        if (jobs.size() <= (1u << 22)) {
-            ChunkPlan pl;
-            pl.n_jobs = (uint32_t)jobs.size();
-            pl.chunk_len = chunk_len;
-            pl.cap = chunk_len / 8 + 4;
-            pl.chunk_stride = MODE == MODE_ENCODE ? ((chunk_len + 5 * chunk_len / 16 + 160 + 15) & ~15u) : 0;
-            CHK(ensure(c, cb.d_jobs, jobs.size() * sizeof(ChunkJob), st));
-            CHK(ensure(c, cb.d_seg0, seg0.size() * 4, st));
-            if (cb.logs_ahead.valid()) { // (allocated ahead by a helper thread: see ChunkBufs)
-                DevBuf ahead = cb.logs_ahead.get();
-                if (ahead.p && ahead.cap > cb.d_logs.cap) { // (otherwise it goes back as `ahead` goes)
-                    if (cb.d_logs.p)
-                        HIPCHK(c, hipStreamSynchronize(st));
-                    cb.d_logs = std::move(ahead);
-                }
-            }
-            CHK(ensure(c, cb.d_logs, jobs.size() * (size_t)pl.cap * sizeof(ChunkState), st));
-            CHK(ensure(c, cb.d_logn, jobs.size() * 4, st));
-            if (MODE == MODE_ENCODE)
-                CHK(ensure(c, cb.d_out, jobs.size() * (size_t)pl.chunk_stride + 64, st));
-            CHK(upload(c, cb.d_jobs.p, jobs.data(), jobs.size() * sizeof(ChunkJob), st)); // (a window of diverged genomes has a few 10 k chunks)
-            CHK(upload(c, cb.d_seg0.p, seg0.data(), seg0.size() * 4, st));
-            pl.jobs = (const ChunkJob *)cb.d_jobs.p;
-            pl.seg_chunk0 = (const uint32_t *)cb.d_seg0.p;
-            pl.logs = (ChunkState *)cb.d_logs.p;
-            pl.log_n = (uint32_t *)cb.d_logn.p;
-            pl.chunk_out = (uint8_t *)cb.d_out.p;
-            static const bool chunk_log = getenv("AGC_HIP_CHUNK_LOG") != nullptr; // (a measuring aid: every chunked launch on stderr)
-            Event ev[3];
-            if (chunk_log)
-                for (auto &e : ev)
-                    (void)hipEventCreate(&e.h);
-            {
-                KTimer t(c, lane ? -1 : MODE == MODE_ENCODE ? AGC_HIP_K_ENCODE : MODE == MODE_ESTIMATE ? AGC_HIP_K_ESTIMATE : AGC_HIP_K_COSTVEC);
-                if (chunk_log)
-                    (void)hipEventRecord(ev[0], st);
-                hipLaunchKernelGGL(lz_chunk_kernel<MODE>, dim3((pl.n_jobs + 3) / 4), dim3(256), 0, st, d_refs, d_segs, pl, out_u32);
-                if (chunk_log)
-                    (void)hipEventRecord(ev[1], st);
-                hipLaunchKernelGGL(lz_hop_kernel<MODE>, dim3(grid), dim3(256), 0, st, d_refs, d_segs, n, pl, out_bytes, out_u32, d_resv, d_resp);
-                if (chunk_log)
-                    (void)hipEventRecord(ev[2], st);
-            }
-            HIPCHK(c, hipGetLastError());
-            if (chunk_log) {
-                (void)hipEventSynchronize(ev[2]);
-                float a = 0, b2 = 0;
-                (void)hipEventElapsedTime(&a, ev[0], ev[1]);
-                (void)hipEventElapsedTime(&b2, ev[1], ev[2]);
-                uint64_t total = 0;
-                for (const SegDesc &sd : b->segs)
-                    total += sd.text.len;
-                fprintf(stderr, "    chunked launch mode %d: %u texts, %.2f Mb, longest %u, %u chunks of %u: chunk kernel %.3f ms, hop kernel %.3f ms\n", MODE, n, total / 1e6,
-                        (uint32_t)b->segs[0].text.len, pl.n_jobs, chunk_len, a, b2);
-                if (MODE != MODE_ESTIMATE) { // (the hop parser left its counters where an estimate's peak goes)
-                    std::vector<uint32_t> dbg(n);
-                    (void)hipMemcpy(dbg.data(), d_resp, (size_t)n * 4, hipMemcpyDeviceToHost);
-                    uint32_t shown = 0;
-                    for (uint32_t i = 0; i < n && shown < 16; ++i) {
-                        const uint32_t nch = ((uint32_t)b->segs[i].text.len + chunk_len - 1) / chunk_len, hops = dbg[b->segs[i].idx] >> 16;
-                        if (i >= 4 && (hops * 2 >= nch || nch < 4))
-                            continue; // (the first few, and every text the hop wavefront had to parse mostly by itself)
-                        ++shown;
-                        fprintf(stderr, "        text %u: %u symbols (rc %u), %u chunks, ref %u (gid %u): %u chunks taken over, %u matches parsed by the hop wavefront\n", i,
-                                (uint32_t)b->segs[i].text.len, (uint32_t)b->segs[i].text.rc, nch, c->refs[b->segs[i].ref_slot].ref_size, b->segs[i].ref_slot, hops,
-                                dbg[b->segs[i].idx] & 0xFFFFu);
-                    }
-                }
-            }
-            return AGC_HIP_OK;
-        }
-    }
-    if (b && !n_dev && MODE != MODE_ENCODE && forced != 0 && n >= 1024) {
-        // a big batch that was not worth chunks: the next one may be -- have the logs ready (sized for this batch's text + a half)
-        agc_hip_ctx::ChunkBufs &cb = c->chunk_bufs[lane];
-        if (!cb.logs_asked) {
-            uint64_t total = 0;
-            for (const SegDesc &sd : b->segs)
-                total += sd.text.len;
-            const size_t n_jobs = (size_t)(total / 4096 + n), want = (n_jobs + n_jobs / 2) * (size_t)(4096 / 8 + 4) * sizeof(ChunkState);
-            if (total >= (32u << 20) && cb.d_logs.cap < want) { // (the few-texts launches of every step leave a small buffer behind)
-                cb.logs_asked = true;
-                const int dev = c->device;
-                cb.logs_ahead = std::async(std::launch::async, [want, dev] {
-                    DevBuf d;
-                    if (hipSetDevice(dev) == hipSuccess && hipMalloc(&d.p, want) == hipSuccess)
-                        d.cap = want;
-                    else
-                        d.p = nullptr;
-                    return d;
-                });
-            }
-        }
-    }
-    static const bool chunk_log2 = getenv("AGC_HIP_CHUNK_LOG") != nullptr;
-    Event pe[2];
-    if (chunk_log2 && b)
-        for (auto &e : pe)
-            (void)hipEventCreate(&e.h);
-    {
-        KTimer t(c, lane ? -1 : MODE == MODE_ENCODE ? AGC_HIP_K_ENCODE : MODE == MODE_ESTIMATE ? AGC_HIP_K_ESTIMATE : AGC_HIP_K_COSTVEC);
-        if (pe[0])
-            (void)hipEventRecord(pe[0], st);
-        hipLaunchKernelGGL(lz_parse_kernel<MODE>, dim3(grid), dim3(256), 0, st, d_refs, d_segs, n, out_bytes, out_u32, d_resv, d_resp, n_dev);
-        if (pe[0])
-            (void)hipEventRecord(pe[1], st);
-    }
-    if (pe[0]) {
-        (void)hipEventSynchronize(pe[1]);
-        float a = 0;
-        (void)hipEventElapsedTime(&a, pe[0], pe[1]);
-        uint64_t total = 0;
-        for (const SegDesc &sd : b->segs)
-            total += sd.text.len;
-        fprintf(stderr, "    whole-text launch mode %d: %u texts, %.2f Mb, longest %u: %.3f ms\n", MODE, n, total / 1e6, n ? (uint32_t)b->segs[0].text.len : 0u, a);
-    }
-    HIPCHK(c, hipGetLastError());
+    CHK(ensure(c, cb.d_logs, jobs.size() * (size_t)pl.cap * sizeof(ChunkState), L.s));
+    CHK(ensure(c, cb.d_logn, jobs.size() * 4, L.s));
+    if (encode)
+        CHK(ensure(c, cb.d_out, jobs.size() * (size_t)pl.chunk_stride + 64, L.s));
+    CHK(upload(c, cb.d_jobs.p, jobs.data(), jobs.size() * sizeof(ChunkJob), L.s)); // (a window of diverged genomes has a few 10 k chunks)
+    CHK(upload(c, cb.d_seg0.p, seg0.data(), seg0.size() * 4, L.s));
+    pl.jobs = (const ChunkJob *)cb.d_jobs.p;
+    pl.seg_chunk0 = (const uint32_t *)cb.d_seg0.p;
+    pl.logs = (ChunkState *)cb.d_logs.p;
+    pl.log_n = (uint32_t *)cb.d_logn.p;
+    pl.chunk_out = (uint8_t *)cb.d_out.p;
     return AGC_HIP_OK;
 }
 
-// The deltas of a parsed batch, back to back on the host: offsets from their lengths, one gather, one copy, waited for on `st`.
-// `b`: the buffers of the stream that parsed (the first stream's or a lane's).  direct: a pinned h_enc (agc_hip_host_alloc) is
-// written by the gather itself, over the link -- no second buffer, no copy engine; anything else, and every result of the one-call
-// encode, gets the deltas compacted in HBM and copied.
-struct EncBufs {
-    DevBuf &scratch, &segs, &resv, &dstoff, &compact;
+// a big batch that was not worth chunks: the next one may be -- a helper thread has the logs ready (once per lane)
+void ask_logs_ahead(agc_hip_ctx *c, LzLane::Chunks &cb, bool encode, uint32_t n, uint64_t text_total)
+{
+    const size_t want = cb.logs_asked ? 0 : (size_t)lp::logs_ahead_bytes(encode, n, text_total, cb.d_logs.cap, sizeof(ChunkState));
+    if (!want)
+        return;
+    cb.logs_asked = true;
+    cb.logs_ahead = std::async(std::launch::async, [want, dev = c->device] {
+        DevBuf d;
+        if (hipSetDevice(dev) == hipSuccess && hipMalloc(&d.p, want) == hipSuccess)
+            d.cap = want;
+        else
+            d.p = nullptr;
+        return d;
+    });
+}
+
+// AGC_HIP_CHUNK_LOG (a measuring aid): every parse launch the host has descriptors of on stderr, timed by events of its own
+struct ChunkLog {
+    Event ev[3];
+    int marks = 0;
+    bool on;
+    explicit ChunkLog(bool has_batch)
+    {
+        static const bool asked = getenv("AGC_HIP_CHUNK_LOG") != nullptr;
+        on = asked && has_batch;
+        for (int i = 0; on && i < 3; ++i)
+            on = hipEventCreate(&ev[i].h) == hipSuccess;
+    }
+    void mark(hipStream_t st)
+    {
+        if (on)
+            (void)hipEventRecord(ev[marks++], st);
+    }
+    // pl.n_jobs == 0: a whole-text launch (two marks); otherwise the chunk kernel and the hop kernel (three)
+    void print(const agc_hip_ctx *c, int mode, const Batch &b, const ChunkPlan &pl, const uint32_t *d_resp)
+    {
+        if (!on)
+            return;
+        const uint32_t n = (uint32_t)b.segs.size(), longest = n ? b.segs[0].text.len : 0u;
+        (void)hipEventSynchronize(ev[marks - 1]);
+        float t1 = 0, t2 = 0;
+        (void)hipEventElapsedTime(&t1, ev[0], ev[1]);
+        if (!pl.n_jobs) {
+            fprintf(stderr, "    whole-text launch mode %d: %u texts, %.2f Mb, longest %u: %.3f ms\n", mode, n, b.text_total / 1e6, longest, t1);
+            return;
+        }
+        (void)hipEventElapsedTime(&t2, ev[1], ev[2]);
+        fprintf(stderr, "    chunked launch mode %d: %u texts, %.2f Mb, longest %u, %u chunks of %u: chunk kernel %.3f ms, hop kernel %.3f ms\n", mode, n, b.text_total / 1e6,
+                longest, pl.n_jobs, pl.chunk_len, t1, t2);
+        if (mode == MODE_ESTIMATE) // (elsewhere the hop parser left its counters where an estimate's peak goes)
+            return;
+        std::vector<uint32_t> dbg(n);
+        (void)hipMemcpy(dbg.data(), d_resp, (size_t)n * 4, hipMemcpyDeviceToHost);
+        uint32_t shown = 0;
+        for (uint32_t i = 0; i < n && shown < 16; ++i) {
+            const SegDesc &sd = b.segs[i];
+            const uint32_t nch = (sd.text.len + pl.chunk_len - 1) / pl.chunk_len, hops = dbg[sd.idx] >> 16;
+            if (i >= 4 && (hops * 2 >= nch || nch < 4))
+                continue; // (the first few, and every text the hop wavefront had to parse mostly by itself)
+            ++shown;
+            fprintf(stderr, "        text %u: %u symbols (rc %u), %u chunks, ref %u (gid %u): %u chunks taken over, %u matches parsed by the hop wavefront\n", i, sd.text.len,
+                    sd.text.rc, nch, c->refs[sd.ref_slot].ref_size, sd.ref_slot, hops, dbg[sd.idx] & 0xFFFFu);
+        }
+    }
 };
 
-int collect_deltas(agc_hip_ctx *c, EncBufs b, hipStream_t st, uint32_t n, const uint32_t *lens, bool direct, uint8_t *h_enc, uint64_t enc_cap, uint64_t *h_enc_off,
-                   Laps LAP)
+// The parse of the n descriptors in L.d_segs, on the lane's stream.  n_dev: their number was made on the device (n is an upper bound);
+// b: the batch the host made them from.  A launch with few, long texts is a handful of dependent chains on an empty GPU: such batches
+// are parsed in chunks (lz_kernels.hip: ChunkCtl) -- a wavefront per 4096-symbol chunk, then a wavefront per text that joins them.
+// AGC_HIP_LZ_CHUNK=<symbols> forces a chunk length for every launch the host has descriptors of (the tests run the whole LZ suite
+// that way), 0 switches the path off.
+template <int MODE>
+int launch_parse(agc_hip_ctx *c, LzLane &L, uint32_t n, uint8_t *out_bytes, uint32_t *out_u32, const uint32_t *n_dev = nullptr, const Batch *b = nullptr)
+{
+    static const int forced = getenv("AGC_HIP_LZ_CHUNK") ? atoi(getenv("AGC_HIP_LZ_CHUNK")) : -1;
+    const bool has_batch = b && !n_dev && b->segs.size() == n;
+    const RefDesc *d_refs = (const RefDesc *)c->d_refs.p;
+    const SegDesc *d_segs = (const SegDesc *)L.d_segs.p;
+    uint32_t *d_resv = (uint32_t *)L.d_resv.p, *d_resp = (uint32_t *)L.d_resp.p;
+    ChunkPlan pl{};
+    if (const uint32_t chunk_len = lp::chunk_len_for(forced, has_batch, n, has_batch && n ? b->segs[0].text.len : 0u, has_batch ? b->text_total : 0))
+        CHK(place_chunks(c, L, *b, chunk_len, MODE == MODE_ENCODE, pl));
+    if (!pl.n_jobs && has_batch && forced != 0)
+        ask_logs_ahead(c, L.chunks, MODE == MODE_ENCODE, n, b->text_total);
+    ChunkLog log(has_batch);
+    {
+        // (KTimer records on the steps' stream: an encode lane times its launch with its own events)
+        KTimer t(c, L.s != c->stream ? -1 : MODE == MODE_ENCODE ? AGC_HIP_K_ENCODE : MODE == MODE_ESTIMATE ? AGC_HIP_K_ESTIMATE : AGC_HIP_K_COSTVEC);
+        const uint32_t grid = (n + 3) / 4; // one wave per segment, 4 waves per block
+        log.mark(L.s);
+        if (pl.n_jobs) {
+            hipLaunchKernelGGL(lz_chunk_kernel<MODE>, dim3((pl.n_jobs + 3) / 4), dim3(256), 0, L.s, d_refs, d_segs, pl, out_u32);
+            log.mark(L.s);
+            hipLaunchKernelGGL(lz_hop_kernel<MODE>, dim3(grid), dim3(256), 0, L.s, d_refs, d_segs, n, pl, out_bytes, out_u32, d_resv, d_resp);
+        } else
+            hipLaunchKernelGGL(lz_parse_kernel<MODE>, dim3(grid), dim3(256), 0, L.s, d_refs, d_segs, n, out_bytes, out_u32, d_resv, d_resp, n_dev);
+        log.mark(L.s);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (has_batch)
+        log.print(c, MODE, *b, pl, d_resp);
+    return AGC_HIP_OK;
+}
+
+// The deltas of a batch parsed on lane L, back to back on the host: offsets from their lengths, one gather, one copy, waited for on
+// the lane's stream.  direct: a pinned h_enc (agc_hip_host_alloc) is written by the gather itself, over the link -- no second
+// buffer, no copy engine; anything else, and every result of the one-call encode, gets the deltas compacted in HBM and copied.
+int collect_deltas(agc_hip_ctx *c, LzLane &L, uint32_t n, const uint32_t *lens, bool direct, uint8_t *h_enc, uint64_t enc_cap, uint64_t *h_enc_off, Laps LAP)
 {
     for (uint32_t i = 0; i < n; ++i)
         h_enc_off[i + 1] = h_enc_off[i] + lens[i];
@@ -2151,22 +2046,22 @@ int collect_deltas(agc_hip_ctx *c, EncBufs b, hipStream_t st, uint32_t n, const 
         return AGC_HIP_OK;
     if (!h_enc)
         return AGC_HIP_EINVAL;
-    CHK(ensure(c, b.dstoff, (size_t)n * 8, st));
-    CHK(upload(c, b.dstoff.p, h_enc_off, (size_t)n * 8, st));
+    CHK(ensure(c, L.d_dstoff, (size_t)n * 8, L.s));
+    CHK(upload(c, L.d_dstoff.p, h_enc_off, (size_t)n * 8, L.s));
     void *d_host = nullptr;
     if (direct && hipHostGetDevicePointer(&d_host, h_enc, 0) != hipSuccess) {
         (void)hipGetLastError();
         d_host = nullptr;
     }
     if (!d_host)
-        CHK(ensure(c, b.compact, tot, st));
-    hipLaunchKernelGGL(gather_bytes_kernel, dim3(grid_for(n, 1, 8192)), dim3(256), 0, st, (const uint8_t *)b.scratch.p, (const SegDesc *)b.segs.p,
-                       (const uint32_t *)b.resv.p, (const uint64_t *)b.dstoff.p, n, d_host ? (uint8_t *)d_host : (uint8_t *)b.compact.p);
+        CHK(ensure(c, L.d_compact, tot, L.s));
+    hipLaunchKernelGGL(gather_bytes_kernel, dim3(grid_for(n, 1, 8192)), dim3(256), 0, L.s, (const uint8_t *)L.d_scratch.p, (const SegDesc *)L.d_segs.p,
+                       (const uint32_t *)L.d_resv.p, (const uint64_t *)L.d_dstoff.p, n, d_host ? (uint8_t *)d_host : (uint8_t *)L.d_compact.p);
     HIPCHK(c, hipGetLastError());
     if (!d_host)
-        HIPCHK(c, hipMemcpyAsync(h_enc, b.compact.p, tot, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(h_enc, L.d_compact.p, tot, hipMemcpyDeviceToHost, L.s));
     LAP("queued");
-    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipStreamSynchronize(L.s));
     LAP("deltas on the host");
     return AGC_HIP_OK;
 }
@@ -2176,32 +2071,31 @@ int collect_deltas(agc_hip_ctx *c, EncBufs b, hipStream_t st, uint32_t n, const 
 static int lz_encode_impl(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const PackedSrc &src, const uint64_t *h_off, const uint32_t *h_len,
                           const uint8_t *h_rc, uint8_t *h_enc, uint64_t enc_cap, uint64_t *h_enc_off)
 {
+    LzLane &L = c->lane(0);
     Batch b;
-    CHK(prepare_batch(c, MODE_ENCODE, n, h_gid, src, h_off, h_len, h_rc, nullptr, b));
-    CHK(ensure(c, c->d_scratch, b.out_total + 64));
-    CHK(launch_parse<MODE_ENCODE>(c, n, (uint8_t *)c->d_scratch.p, nullptr, 0, nullptr, &b));
+    CHK(prepare_batch(c, L, MODE_ENCODE, n, h_gid, src, h_off, h_len, h_rc, nullptr, b));
+    CHK(ensure(c, L.d_scratch, b.out_total + 64));
+    CHK(launch_parse<MODE_ENCODE>(c, L, n, (uint8_t *)L.d_scratch.p, nullptr, nullptr, &b));
     std::vector<uint32_t> lens(n);
-    HIPCHK(c, hipMemcpyAsync(lens.data(), c->d_resv.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return collect_deltas(c, {c->d_scratch, c->d_segs, c->d_resv, c->d_dstoff, c->d_compact}, c->stream, n, lens.data(), false, h_enc, enc_cap, h_enc_off,
-                          Laps("", 0));
+    HIPCHK(c, hipMemcpyAsync(lens.data(), L.d_resv.p, (size_t)n * 4, hipMemcpyDeviceToHost, L.s));
+    HIPCHK(c, hipStreamSynchronize(L.s));
+    return collect_deltas(c, L, n, lens.data(), false, h_enc, enc_cap, h_enc_off, Laps("", 0));
 }
 
-// The encode in two halves (include/agc_hip.h): begin queues the parse and the copy of the delta lengths on the context's second
+// The encode in two halves (include/agc_hip.h): begin queues the parse and the copy of the delta lengths on an encode lane's
 // stream and returns; end waits, lays the deltas out back to back and brings them over.  Between the two the caller may use every
 // other entry point (they run on the first stream with their own scratch).
-static int lz_encode_begin_impl(agc_hip_ctx *c, int lane, uint32_t n, const uint32_t *h_gid, const PackedSrc &src, const uint64_t *h_off,
+static int lz_encode_begin_impl(agc_hip_ctx *c, LzLane &L, uint32_t n, const uint32_t *h_gid, const PackedSrc &src, const uint64_t *h_off,
                                 const uint32_t *h_len, const uint8_t *h_rc)
 {
-    agc_hip_ctx::Lane2 &L = c->lane(lane);
     Batch b;
-    CHK(prepare_batch(c, MODE_ENCODE, n, h_gid, src, h_off, h_len, h_rc, nullptr, b, lane));
+    CHK(prepare_batch(c, L, MODE_ENCODE, n, h_gid, src, h_off, h_len, h_rc, nullptr, b));
     CHK(ensure(c, L.d_scratch, b.out_total + 64, L.s));
     CHK(ensure_pinned(c, L.h_lens, (size_t)n * 4, ((size_t)n + n / 4 + 1024) * 4));
     L.timed = c->timing;
     if (L.timed)
         (void)hipEventRecord(L.e0, L.s);
-    CHK(launch_parse<MODE_ENCODE>(c, n, (uint8_t *)L.d_scratch.p, nullptr, lane, nullptr, &b));
+    CHK(launch_parse<MODE_ENCODE>(c, L, n, (uint8_t *)L.d_scratch.p, nullptr, nullptr, &b));
     if (L.timed)
         (void)hipEventRecord(L.e1, L.s);
     HIPCHK(c, hipEventRecord(L.done, L.s));
@@ -2212,9 +2106,8 @@ static int lz_encode_begin_impl(agc_hip_ctx *c, int lane, uint32_t n, const uint
 }
 
 // common start of the two begin entry points: an abandoned encode is dropped, the first stream's work so far comes first
-static int lz_encode_begin_enter(agc_hip_ctx *c, int lane, uint32_t n)
+static int lz_encode_begin_enter(agc_hip_ctx *c, LzLane &L, uint32_t n)
 {
-    agc_hip_ctx::Lane2 &L = c->lane(lane);
     if (L.pending) { // (an abandoned encode: a caller that failed between the two halves) -- dropped
         HIPCHK(c, hipStreamSynchronize(L.s));
         L.pending = false;
@@ -2267,10 +2160,11 @@ int agc_hip_lz_encode_begin_packed_on(agc_hip_ctx *c, uint32_t lane, uint32_t n,
 {
     if (!c || lane >= AGC_HIP_ENCODE_LANES || (n && (!h_gid || !h_off || !h_len || !pk || !pk->d_words)))
         return AGC_HIP_EINVAL;
-    const int e = lz_encode_begin_enter(c, (int)lane + 1, n);
+    LzLane &L = c->lane((int)lane + 1);
+    const int e = lz_encode_begin_enter(c, L, n);
     if (e)
         return e > 0 ? AGC_HIP_OK : e;
-    return lz_encode_begin_impl(c, (int)lane + 1, n, h_gid, src_of(pk), h_off, h_len, h_rc);
+    return lz_encode_begin_impl(c, L, n, h_gid, src_of(pk), h_off, h_len, h_rc);
 }
 
 int agc_hip_lz_encode_begin_packed(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const agc_hip_packed *pk, const uint64_t *h_off,
@@ -2284,12 +2178,12 @@ int agc_hip_lz_encode_begin_dev(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gi
 {
     if (!c || (n && (!h_gid || !h_off || !h_len || !d_base)))
         return AGC_HIP_EINVAL;
-    const int e = lz_encode_begin_enter(c, 1, n);
+    LzLane &L = c->lane(1); // (the lane's own packed copy: it lives until end)
+    const int e = lz_encode_begin_enter(c, L, n);
     if (e)
         return e > 0 ? AGC_HIP_OK : e;
-    agc_hip_ctx::Lane2 &L = c->lane(1); // (the lane's own packed copy: it lives until end)
     return with_packed_bytes(c, d_base, n, h_off, h_len, L.pk, L.s, [&](const PackedSrc &src, const uint64_t *off2) {
-        return lz_encode_begin_impl(c, 1, n, h_gid, src, off2, h_len, h_rc);
+        return lz_encode_begin_impl(c, L, n, h_gid, src, off2, h_len, h_rc);
     });
 }
 
@@ -2299,7 +2193,7 @@ int agc_hip_lz_encode_pending_on(agc_hip_ctx *c, uint32_t lane, uint32_t *h_n)
 {
     if (!c || !h_n || lane >= AGC_HIP_ENCODE_LANES)
         return AGC_HIP_EINVAL;
-    agc_hip_ctx::Lane2 &L = c->lane((int)lane + 1);
+    LzLane &L = c->lane((int)lane + 1);
     *h_n = 0;
     if (!L.pending)
         return AGC_HIP_OK;
@@ -2317,7 +2211,7 @@ int agc_hip_lz_encode_drop_on(agc_hip_ctx *c, uint32_t lane)
 {
     if (!c || lane >= AGC_HIP_ENCODE_LANES)
         return AGC_HIP_EINVAL;
-    agc_hip_ctx::Lane2 &L = c->lane((int)lane + 1);
+    LzLane &L = c->lane((int)lane + 1);
     if (L.pending) {
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, hipStreamSynchronize(L.s));
@@ -2338,7 +2232,7 @@ int agc_hip_lz_encode_end_on(agc_hip_ctx *c, uint32_t lane, uint8_t *h_enc, uint
 {
     if (!c || !h_enc_off || lane >= AGC_HIP_ENCODE_LANES)
         return AGC_HIP_EINVAL;
-    agc_hip_ctx::Lane2 &L = c->lane((int)lane + 1);
+    LzLane &L = c->lane((int)lane + 1);
     if (!L.pending) {
         c->err = "lz_encode_end: no encode in flight";
         return AGC_HIP_EINVAL;
@@ -2384,7 +2278,7 @@ int agc_hip_lz_encode_end_on(agc_hip_ctx *c, uint32_t lane, uint8_t *h_enc, uint
     }
 #endif
     // (AGC_HIP_ECAP: still in flight -- call again with a larger buffer)
-    CHK(collect_deltas(c, {L.d_scratch, L.d_segs, L.d_resv, L.d_dstoff, L.d_compact}, L.s, n, L.h_lens.as<uint32_t>(), true, h_enc, enc_cap, h_enc_off, Laps("lz_encode_end", n)));
+    CHK(collect_deltas(c, L, n, L.h_lens.as<uint32_t>(), true, h_enc, enc_cap, h_enc_off, Laps("lz_encode_end", n)));
     L.pending = false;
     return AGC_HIP_OK;
 }
@@ -2431,27 +2325,29 @@ int agc_hip_host_free(agc_hip_ctx *c, void *p)
 static int lz_estimate_impl(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const PackedSrc &src, const uint64_t *h_off, const uint32_t *h_len,
                             const uint8_t *h_rc, uint32_t *h_cost, uint32_t *h_peak)
 {
+    LzLane &L = c->lane(0);
     Batch b;
-    CHK(prepare_batch(c, MODE_ESTIMATE, n, h_gid, src, h_off, h_len, h_rc, nullptr, b));
-    CHK(launch_parse<MODE_ESTIMATE>(c, n, nullptr, nullptr, 0, nullptr, &b));
-    HIPCHK(c, hipMemcpyAsync(h_cost, c->d_resv.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    CHK(prepare_batch(c, L, MODE_ESTIMATE, n, h_gid, src, h_off, h_len, h_rc, nullptr, b));
+    CHK(launch_parse<MODE_ESTIMATE>(c, L, n, nullptr, nullptr, nullptr, &b));
+    HIPCHK(c, hipMemcpyAsync(h_cost, L.d_resv.p, (size_t)n * 4, hipMemcpyDeviceToHost, L.s));
     if (h_peak)
-        HIPCHK(c, hipMemcpyAsync(h_peak, c->d_resp.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpyAsync(h_peak, L.d_resp.p, (size_t)n * 4, hipMemcpyDeviceToHost, L.s));
+    HIPCHK(c, hipStreamSynchronize(L.s));
     return AGC_HIP_OK;
 }
 
 static int lz_cost_vector_impl(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const PackedSrc &src, const uint64_t *h_off, const uint32_t *h_len,
                                const uint8_t *h_rc, const uint8_t *h_prefix_costs, uint32_t *h_costs)
 {
+    LzLane &L = c->lane(0);
     Batch b;
-    CHK(prepare_batch(c, MODE_COSTVEC, n, h_gid, src, h_off, h_len, h_rc, h_prefix_costs, b));
-    CHK(ensure(c, c->d_scratch, b.out_total + 64)); // (one byte per position on the device: lz_kernels.hip, cost_t)
-    CHK(launch_parse<MODE_COSTVEC>(c, n, nullptr, (uint32_t *)c->d_scratch.p, 0, nullptr, &b));
+    CHK(prepare_batch(c, L, MODE_COSTVEC, n, h_gid, src, h_off, h_len, h_rc, h_prefix_costs, b));
+    CHK(ensure(c, L.d_scratch, b.out_total + 64)); // (one byte per position on the device: lz_kernels.hip, cost_t)
+    CHK(launch_parse<MODE_COSTVEC>(c, L, n, nullptr, (uint32_t *)L.d_scratch.p, nullptr, &b));
     std::vector<uint8_t> tmp(b.out_total);
     if (b.out_total)
-        HIPCHK(c, hipMemcpyAsync(tmp.data(), c->d_scratch.p, b.out_total, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpyAsync(tmp.data(), L.d_scratch.p, b.out_total, hipMemcpyDeviceToHost, L.s));
+    HIPCHK(c, hipStreamSynchronize(L.s));
     for (uint64_t i = 0; i < b.out_total; ++i)
         h_costs[i] = tmp[i];
     return AGC_HIP_OK;
@@ -2476,10 +2372,11 @@ static int lz_split_point_impl(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid
         pf[2 * s] = h_prefix1[s];
         pf[2 * s + 1] = h_prefix2[s];
     }
+    LzLane &L = c->lane(0); // (the split-point kernel reads the cost vectors out of the parse's scratch and answers into d_dstoff)
     Batch b;
-    CHK(prepare_batch(c, MODE_COSTVEC, m, gid.data(), src, off.data(), len.data(), rc.data(), pf.data(), b));
-    CHK(ensure(c, c->d_scratch, b.out_total + 64));
-    CHK(launch_parse<MODE_COSTVEC>(c, m, nullptr, (uint32_t *)c->d_scratch.p, 0, nullptr, &b));
+    CHK(prepare_batch(c, L, MODE_COSTVEC, m, gid.data(), src, off.data(), len.data(), rc.data(), pf.data(), b));
+    CHK(ensure(c, L.d_scratch, b.out_total + 64));
+    CHK(launch_parse<MODE_COSTVEC>(c, L, m, nullptr, (uint32_t *)L.d_scratch.p, nullptr, &b));
     std::vector<SplitJob> jobs(n);
     uint64_t o = 0;
     for (uint32_t s = 0; s < n; ++s) {
@@ -2492,13 +2389,13 @@ static int lz_split_point_impl(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid
         o += 2ULL * h_len[s];
     }
     CHK(ensure(c, c->d_jobs, (size_t)n * sizeof(SplitJob)));
-    CHK(ensure(c, c->d_dstoff, (size_t)n * 8));
+    CHK(ensure(c, L.d_dstoff, (size_t)n * 8));
     CHK(upload(c, c->d_jobs.p, jobs.data(), (size_t)n * sizeof(SplitJob), c->stream));
-    uint32_t *d_pos = (uint32_t *)c->d_dstoff.p, *d_sum = d_pos + n;
+    uint32_t *d_pos = (uint32_t *)L.d_dstoff.p, *d_sum = d_pos + n;
     {
         KTimer t(c, AGC_HIP_K_COSTVEC);
         hipLaunchKernelGGL(split_point_kernel, dim3(n), dim3(256), 0, c->stream, (const SplitJob *)c->d_jobs.p,
-                           (const cost_t *)c->d_scratch.p, d_pos, d_sum);
+                           (const cost_t *)L.d_scratch.p, d_pos, d_sum);
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(h_best_pos, d_pos, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));

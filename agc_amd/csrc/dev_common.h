@@ -3,11 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sym_view.h"
+#include "lz_consts.h" // HASHING_STEP, REF_TAIL_WORDS, PACK_BLOCK, the key filters' sizes: shared with the host's lz_plan.h
 
 namespace agc {
 
 constexpr uint32_t WAVE = 64;
-constexpr uint32_t HASHING_STEP = 4;     // lz_diff.h:38 (USE_SPARSE_HT)
 constexpr uint32_t MAX_NO_TRIES = 64;    // lz_diff.h:32
 constexpr uint8_t INVALID_SYMBOL = 31;   // lz_diff.h:33
 constexpr uint8_t N_CODE = 4;            // lz_diff.h:34
@@ -32,17 +32,7 @@ constexpr uint32_t MIN_NRUN_LEN = 4;     // lz_diff.h:36
 // collection has, and what fits the LDS of key_filter_kernel), then the next power of two of keys / 4 words (>= 16 bits per key): the
 // 600 kb references of a diverged bacterial collection filled the fixed-size filters to 82 % and 30 % of the foreign positions
 // passed both -- a foreign stretch then costs an exact step every third position, tens of milliseconds per text.
-constexpr uint32_t KEY_BLOOM_HALF = 4096;
-constexpr uint32_t KEY_BLOOM_SHIFT0 = 20; // word index = 32 - shift bits of the hash: 12 bits for KEY_BLOOM_HALF words
-__host__ __device__ inline uint32_t key_bloom_shift(uint32_t ref_size)
-{
-    const uint32_t keys = ref_size / HASHING_STEP + 1;
-    uint32_t sh = KEY_BLOOM_SHIFT0;
-    while (sh > 8 && (1u << (32 - sh)) < keys / 4)
-        --sh;
-    return sh;
-}
-__host__ __device__ inline uint32_t key_bloom_half_words(uint32_t shift) { return 1u << (32 - shift); }
+// (KEY_BLOOM_HALF, key_bloom_shift, key_bloom_half_words: lz_consts.h)
 // The filters as 32-bit words (a half = 2 * key_bloom_half_words u32 words): the word from the top bits of one product, the
 // three bit numbers from the low 5 bits of bytes 1-3 of a second one (the shifter reads them where they lie: SDWA) -- 10 vector
 // instructions per key instead of the ~25 of the 64-bit form of rounds 4-5 (key_filter_kernel tests one key per text position).
@@ -83,7 +73,6 @@ struct RefDesc {
     uint32_t is_short;
     uint32_t valid;
 };
-constexpr uint32_t REF_TAIL_WORDS = 4;
 
 // One sequence to parse: a view into a 2-bit packed buffer (the sample), read reverse-complemented when text.rc.
 struct SegDesc {
@@ -114,7 +103,6 @@ struct ScanRange {
 // +1] of 32-bit word i >> 4.  Blocks of PACK_BLOCK symbols that contain anything outside ACGT (N runs, IUPAC codes) are
 // "escaped": kept verbatim, one byte per symbol, in esc_bytes; esc_index[block] = slot there or -1.  0.25 B per symbol for
 // clean sequence, 1.25 B for escaped blocks.
-constexpr uint32_t PACK_BLOCK = 1024;
 struct PackedView {
     const uint32_t *words;
     const int32_t *esc_index;

@@ -342,9 +342,8 @@ __device__ __forceinline__ uint32_t base_cost_match(uint32_t mml, uint32_t ref_p
 }
 
 // ---------------------------------------------------------------------------
-// The parse, one wavefront per segment.
+// The parse, one wavefront per segment.  (MODE_ENCODE / _ESTIMATE / _COSTVEC and FILTER_CHUNK: lz_consts.h)
 // ---------------------------------------------------------------------------
-enum { MODE_ENCODE = 0, MODE_ESTIMATE = 1, MODE_COSTVEC = 2 };
 // a per-position coding cost (GetCodingCostVector, lz_diff.cpp:159-284): 0 inside a run, 1 per literal, the token's length
 // (a few decimal digits and separators, <= 2 * 10 + 2) at one end of a match or N run -- ONE BYTE in HBM: the vectors are written
 // once and read by split_point_kernel; as 32-bit words they were 1.4 GB written + 2.1 GB read per 3 Gbp sample (round 2)
@@ -1241,7 +1240,6 @@ __global__ void __launch_bounds__(256) gather_bytes_kernel(const uint8_t *__rest
 // multiplies for the filter hash, one LDS read.  Bit = 1 ("may match / let the exact step decide") when the key is in the
 // filter, contains a symbol outside ACGT, or runs past the end of the text.
 // ---------------------------------------------------------------------------
-constexpr uint32_t FILTER_CHUNK = 65536;
 
 struct FilterJob {
     SymView text;

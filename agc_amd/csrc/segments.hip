@@ -91,16 +91,17 @@ static int launch_known(agc_hip_ctx *c)
     uint32_t *flag = (uint32_t *)S.flag, *known_rank = (uint32_t *)S.known_rank;
     unsigned long long *capv = (unsigned long long *)S.capv, *cap_off = (unsigned long long *)S.cap_off;
     SegDesc *descs = (SegDesc *)S.descs;
+    agc_hip_ctx::LzLane &L = c->lane(1);
     CHK(upload_refs(c));
     // a slot = len + 5 len / 16 + 64, rounded up to 16 (known_flag_kernel), and neighbouring segments share k <= 32 symbols:
     // per segment 32 * 21 / 16 + 64 + 15 < 128 bytes beyond its share of the sample
     const size_t scratch_ub = (size_t)(S.total + 5 * S.total / 16) + 128 * (size_t)n_ub + 64;
-    CHK(ensure(c, c->l2.d_segs, (size_t)n_ub * sizeof(SegDesc), c->l2.s));
-    CHK(ensure(c, c->l2.d_resv, (size_t)n_ub * 4, c->l2.s));
-    CHK(ensure(c, c->l2.d_resp, (size_t)n_ub * 4, c->l2.s));
-    CHK(ensure(c, c->l2.d_scratch, scratch_ub, c->l2.s));
-    CHK(ensure(c, c->l2.d_n, 64, c->l2.s));
-    CHK(ensure_pinned(c, c->l2.h_lens, (size_t)n_ub * 4, ((size_t)n_ub + n_ub / 4 + 1024) * 4));
+    CHK(ensure(c, L.d_segs, (size_t)n_ub * sizeof(SegDesc), L.s));
+    CHK(ensure(c, L.d_resv, (size_t)n_ub * 4, L.s));
+    CHK(ensure(c, L.d_resp, (size_t)n_ub * 4, L.s));
+    CHK(ensure(c, L.d_scratch, scratch_ub, L.s));
+    CHK(ensure(c, L.d_n, 64, L.s));
+    CHK(ensure_pinned(c, L.h_lens, (size_t)n_ub * 4, ((size_t)n_ub + n_ub / 4 + 1024) * 4));
     hipLaunchKernelGGL(known_flag_kernel, dim3((n_ub + 256) / 256), dim3(256), 0, st, segs, counts, (const RefDesc *)c->d_refs.p, (uint32_t)c->refs.size(), n_ub, flag,
                        capv);
     hipLaunchKernelGGL(scan_excl_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, flag, known_rank, n_ub + 1);
@@ -113,29 +114,29 @@ static int launch_known(agc_hip_ctx *c)
     HIPCHK(c, hipMemsetAsync(lcnt, 0, (size_t)(3 * (LEN_BUCKETS + 1)) * 4, st));
     hipLaunchKernelGGL(known_len_count_kernel, dim3((n_ub + 255) / 256), dim3(256), 0, st, descs, counts, lcnt);
     hipLaunchKernelGGL(scan_excl_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, lcnt, lstart, LEN_BUCKETS + 1);
-    hipLaunchKernelGGL(known_order_kernel, dim3((n_ub + 255) / 256), dim3(256), 0, st, descs, counts, lstart, lcur, (SegDesc *)c->l2.d_segs.p);
+    hipLaunchKernelGGL(known_order_kernel, dim3((n_ub + 255) / 256), dim3(256), 0, st, descs, counts, lstart, lcur, (SegDesc *)L.d_segs.p);
     HIPCHK(c, hipGetLastError());
     // the number of descriptors moves into a word the lane owns: the next sample's agc_hip_segments_packed clears and re-lays-out
     // the work area on the first stream while this parse (and the copy of the count behind it) may still be running
-    uint32_t *d_n_known = (uint32_t *)c->l2.d_n.p;
+    uint32_t *d_n_known = (uint32_t *)L.d_n.p;
     HIPCHK(c, hipMemcpyAsync(d_n_known, &counts->n_known, 4, hipMemcpyDeviceToDevice, st));
     // the parse on the second lane, behind everything queued here
-    HIPCHK(c, hipEventRecord(c->l2.ready, st));
-    HIPCHK(c, hipStreamWaitEvent(c->l2.s, c->l2.ready, 0));
-    c->l2.timed = c->timing;
-    if (c->l2.timed)
-        (void)hipEventRecord(c->l2.e0, c->l2.s);
-    CHK(launch_parse<MODE_ENCODE>(c, n_ub, (uint8_t *)c->l2.d_scratch.p, nullptr, 1, d_n_known));
-    if (c->l2.timed)
-        (void)hipEventRecord(c->l2.e1, c->l2.s);
-    HIPCHK(c, hipEventRecord(c->l2.done, c->l2.s));
-    c->l2.done_valid = true;
-    HIPCHK(c, hipMemcpyAsync(c->l2.h_lens.p, c->l2.d_resv.p, (size_t)n_ub * 4, hipMemcpyDeviceToHost, c->l2.s));
+    HIPCHK(c, hipEventRecord(L.ready, st));
+    HIPCHK(c, hipStreamWaitEvent(L.s, L.ready, 0));
+    L.timed = c->timing;
+    if (L.timed)
+        (void)hipEventRecord(L.e0, L.s);
+    CHK(launch_parse<MODE_ENCODE>(c, L, n_ub, (uint8_t *)L.d_scratch.p, nullptr, d_n_known));
+    if (L.timed)
+        (void)hipEventRecord(L.e1, L.s);
+    HIPCHK(c, hipEventRecord(L.done, L.s));
+    L.done_valid = true;
+    HIPCHK(c, hipMemcpyAsync(L.h_lens.p, L.d_resv.p, (size_t)n_ub * 4, hipMemcpyDeviceToHost, L.s));
     uint32_t *n_pinned = (uint32_t *)(c->h_segcounts.as<uint8_t>() + 64);
-    HIPCHK(c, hipMemcpyAsync(n_pinned, d_n_known, 4, hipMemcpyDeviceToHost, c->l2.s));
-    c->l2.n_pinned = n_pinned;
-    c->l2.n = 0;
-    c->l2.pending = true;
+    HIPCHK(c, hipMemcpyAsync(n_pinned, d_n_known, 4, hipMemcpyDeviceToHost, L.s));
+    L.n_pinned = n_pinned;
+    L.n = 0;
+    L.pending = true;
     return AGC_HIP_OK;
 }
 
@@ -156,7 +157,8 @@ int agc_hip_segments_packed(agc_hip_ctx *c, const agc_hip_packed *pk, const uint
         return AGC_HIP_OK;
     if (!pk->d_words || !pk->d_esc_index || h_ctg_off[n_ctg] > pk->n_symbols)
         return AGC_HIP_EINVAL;
-    if (encode_known && c->l2.pending) {
+    agc_hip_ctx::LzLane &L = c->lane(1); // (the whole-sample encode's lane)
+    if (encode_known && L.pending) {
         c->err = "segments_packed: the previous encode was not collected (agc_hip_lz_encode_end)";
         return AGC_HIP_EINVAL;
     }
@@ -311,9 +313,9 @@ int agc_hip_segments_packed(agc_hip_ctx *c, const agc_hip_packed *pk, const uint
         if (h_n_encoded)
             *h_n_encoded = ne;
         if (!ne) { // (no group was known: the launch had nothing to do and nothing is in flight)
-            HIPCHK(c, hipStreamSynchronize(c->l2.s));
-            c->l2.n_pinned = nullptr;
-            c->l2.pending = false;
+            HIPCHK(c, hipStreamSynchronize(L.s));
+            L.n_pinned = nullptr;
+            L.pending = false;
         }
     }
     if (from_pf)
@@ -330,7 +332,7 @@ int agc_hip_segments_encode_known(agc_hip_ctx *c)
         c->err = "segments_encode_known: no segments on the device (agc_hip_segments_packed comes first)";
         return AGC_HIP_EINVAL;
     }
-    if (c->l2.pending) {
+    if (c->lane(1).pending) {
         c->err = "segments_encode_known: the previous encode was not collected (agc_hip_lz_encode_end)";
         return AGC_HIP_EINVAL;
     }
