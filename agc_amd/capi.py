@@ -16,9 +16,12 @@ OK, ENODEV, EINVAL, ENOMEM, ECAP, ENOREF = 0, -1, -2, -3, -4, -5
 K_SCAN, K_INDEX, K_ENCODE, K_ESTIMATE, K_COSTVEC, K_REVCOMP, K_PREPROCESS, K_REFSTORE = range(8)
 K_NAMES = ["scan", "index", "encode", "estimate", "costvec", "revcomp", "preprocess", "refstore", "zstd", "filter", "segments", "pack",
            "decode_scan", "decode_write", "fasta_out"]
-K_NAMES_MORE = ["zstd_decode"]  # the slots from 15 on (K_NAMES stays the 15 slots its users count on); timing_get reports both
+K_NAMES_MORE = ["zstd_decode", "parts_unpack"]  # the slots from 15 on (K_NAMES stays the 15 slots its users count on); timing_get reports both
 ZD_OK, ZD_UNSUPPORTED, ZD_MALFORMED = 0, 1, 2
 SEG_RAW, SEG_REF, SEG_DELTA = 0, 1, 2
+PART_STORED, PART_ZSTD = 0, 1
+PART_PACK, PART_REF_BYTES, PART_REF_TUPLES = 0, 1, 2
+PART_OK, PART_BAD_TUPLES = 0, 3  # (a part's status: these, or ZD_UNSUPPORTED / ZD_MALFORMED)
 
 # every symbol include/agc_hip.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
@@ -34,6 +37,7 @@ SYMBOLS = [
     "agc_hip_lz_encode_begin_packed_on", "agc_hip_lz_encode_end_on", "agc_hip_lz_encode_pending_on", "agc_hip_lz_encode_drop_on",
     "agc_hip_lz_decode_batch", "agc_hip_lz_decode_batch_dev",
     "agc_hip_sample_fasta", "agc_hip_sample_fasta_dev",
+    "agc_hip_parts_unpack", "agc_hip_parts_unpack_dev", "agc_hip_sample_fasta_parts", "agc_hip_sample_fasta_parts_dev",
     "agc_hip_host_alloc", "agc_hip_host_free",
     "agc_hip_lz_estimate_batch_dev", "agc_hip_lz_estimate_batch",
     "agc_hip_lz_cost_vector_batch_dev", "agc_hip_lz_cost_vector_batch",
@@ -79,6 +83,8 @@ class SegSrc(C.Structure):
 
 
 SEG_SRC_DTYPE = np.dtype([("kind", "<u4"), ("gid", "<u4"), ("off", "<u8"), ("n_bytes", "<u4"), ("length", "<u4"), ("rc", "<u4"), ("pad", "<u4")])
+PART_DTYPE = np.dtype([("off", "<u8"), ("n_bytes", "<u4"), ("coding", "<u4"), ("content", "<u4"), ("gid", "<u4")])  # agc_hip_part
+SEG_PART_DTYPE = np.dtype([("kind", "<u4"), ("gid", "<u4"), ("part", "<u4"), ("index", "<u4"), ("length", "<u4"), ("rc", "<u4")])  # agc_hip_seg_part
 SEGMENT_DTYPE = np.dtype([("start", "<u8"), ("front_dir", "<u8"), ("front_rc", "<u8"), ("back_dir", "<u8"), ("back_rc", "<u8"), ("ctg", "<u4"), ("len", "<u4"),
                           ("map_gid", "<i4"), ("front_full", "u1"), ("back_full", "u1"), ("store_rc", "u1"), ("encoded", "u1")])
 GROUP_SLOT_DTYPE = np.dtype([("k1", "<u8"), ("k2", "<u8"), ("gid", "<i4"), ("used", "<u4")])
@@ -144,6 +150,12 @@ def load():
     fasta_head = [vp, C.c_uint32, u64p, C.POINTER(SegSrc), u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_char_p, u64p]
     L.agc_hip_sample_fasta.argtypes = fasta_head + [vp, C.c_uint64, u64p]
     L.agc_hip_sample_fasta_dev.argtypes = fasta_head + [vp, C.c_uint64, u64p]
+    parts_head = [vp, C.c_uint32, vp, vp, C.c_uint64, C.c_uint32]  # ctx, n_parts, parts, src, src_bytes, seq_cap
+    L.agc_hip_parts_unpack.argtypes = parts_head + [vp, C.c_uint64, u64p, u32p, u32p, u32p]
+    L.agc_hip_parts_unpack_dev.argtypes = parts_head + [vp, C.c_uint64, u64p, u32p, u32p, u32p]
+    fasta_parts = parts_head + [C.c_uint32, u64p, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, u64p, vp, C.c_uint64, u64p]
+    L.agc_hip_sample_fasta_parts.argtypes = fasta_parts
+    L.agc_hip_sample_fasta_parts_dev.argtypes = fasta_parts
     L.agc_hip_host_alloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
     L.agc_hip_host_free.argtypes = [vp, vp]
     L.agc_hip_lz_estimate_batch_dev.argtypes = [vp, C.c_uint32, u32p, vp, u64p, u32p, u8p, u32p, u32p]
@@ -495,6 +507,11 @@ class Context:
         r = _a(rc, np.uint8) if rc is not None else None
         self._chk(self.L.agc_hip_ref_register_batch_packed(self.h, g.size, _p(g, u32p), C.byref(pk), _p(o, u64p), _p(l, u32p), _p(r, u8p), min_match_len))
 
+    def ref_registered(self, gid):
+        """whether the group has a registered reference (agc_hip_ref_get answers ENOREF for one that has none)"""
+        n = C.c_uint32()
+        return self.L.agc_hip_ref_get(self.h, int(gid), None, 0, C.byref(n)) != ENOREF
+
     def ref_get(self, gid):
         n = C.c_uint32()
         rc = self.L.agc_hip_ref_get(self.h, gid, None, 0, C.byref(n))
@@ -689,6 +706,57 @@ class Context:
     def sample_fasta_dev(self, ctg_seg, segs, data, k, line_length, names, name_off, d_text, text_cap):
         """the same, the text left at the device address d_text (text_cap bytes) -> its length"""
         rc_, n = self.sample_fasta_raw(self.L.agc_hip_sample_fasta_dev, ctg_seg, segs, data, k, line_length, names, name_off, d_text, text_cap)
+        self._chk(rc_)
+        return n
+
+    @staticmethod
+    def _parts_args(parts, src):
+        """parts: PART_DTYPE; src: the buffer their offsets count in -- a bytes-like / uint8 array, or (address, size)"""
+        pt = np.ascontiguousarray(parts, dtype=PART_DTYPE)
+        if isinstance(src, tuple):
+            return pt, src[0], int(src[1]), None
+        s = np.frombuffer(src, np.uint8) if isinstance(src, (bytes, bytearray, memoryview)) else _a(src, np.uint8)
+        return pt, (s.ctypes.data if s.size else None), s.size, s
+
+    def parts_unpack_raw(self, parts, src, seq_cap, out_ptr, out_cap, dev=False, fill=0):
+        """the entry point itself (agc_hip_parts_unpack, dev: _dev) -> (return code, out_off[n+1], counts[n], seq_end[n, seq_cap],
+        statuses[n]); what the call leaves alone keeps the value `fill`"""
+        pt, sp, sn, _keep = self._parts_args(parts, src)
+        n = pt.size
+        ooff = np.zeros(n + 1, np.uint64)
+        cnt, ends, st = np.full(n, fill, np.uint32), np.full((n, seq_cap), fill, np.uint32), np.full(n, fill, np.uint32)
+        fn = self.L.agc_hip_parts_unpack_dev if dev else self.L.agc_hip_parts_unpack
+        rc_ = fn(self.h, n, pt.ctypes.data, sp, sn, int(seq_cap), out_ptr, int(out_cap), _p(ooff, u64p), _p(cnt, u32p), _p(ends, u32p), _p(st, u32p))
+        return rc_, ooff, cnt, ends, st
+
+    def parts_unpack(self, parts, src, seq_cap):
+        """archive parts (PART_DTYPE, their bytes in src) -> (list of their final bytes -- None for a refused part --, counts, seq_end,
+        statuses).  A part is refused on its own: the others of the batch are complete."""
+        rc_, ooff, cnt, ends, st = self.parts_unpack_raw(parts, src, seq_cap, None, 0)
+        if rc_ == ECAP:
+            out = np.empty(int(ooff[-1]), np.uint8)
+            rc_, ooff, cnt, ends, st = self.parts_unpack_raw(parts, src, seq_cap, out.ctypes.data, out.size)
+        else:
+            out = np.zeros(0, np.uint8)
+        if rc_ != EINVAL or not st.any():
+            self._chk(rc_)
+        return [None if st[i] else out[int(ooff[i]):int(ooff[i + 1])].tobytes() for i in range(st.size)], cnt, ends, st
+
+    def sample_fasta_parts_raw(self, parts, src, seq_cap, ctg_seg, segs, k, min_match_len, line_length, names, name_off, text_ptr, text_cap, dev=False):
+        """the entry point itself (agc_hip_sample_fasta_parts, dev: _dev) -> (return code, text length); segs: SEG_PART_DTYPE"""
+        pt, sp, sn, _keep = self._parts_args(parts, src)
+        cs, no = _a(ctg_seg, np.uint64), _a(name_off, np.uint64)
+        sg = np.ascontiguousarray(segs, dtype=SEG_PART_DTYPE)
+        assert cs.size >= 1 and no.size == cs.size and (cs.size == 1 or int(cs[-1]) == sg.size)
+        n = C.c_uint64(0)
+        fn = self.L.agc_hip_sample_fasta_parts_dev if dev else self.L.agc_hip_sample_fasta_parts
+        rc_ = fn(self.h, pt.size, pt.ctypes.data, sp, sn, int(seq_cap), cs.size - 1, _p(cs, u64p), sg.ctypes.data, int(k), int(min_match_len), int(line_length),
+                 bytes(names), _p(no, u64p), text_ptr, int(text_cap), C.byref(n))
+        return rc_, n.value
+
+    def sample_fasta_parts_dev(self, parts, src, seq_cap, ctg_seg, segs, k, min_match_len, line_length, names, name_off, d_text, text_cap):
+        """the text left at the device address d_text (text_cap bytes) -> its length"""
+        rc_, n = self.sample_fasta_parts_raw(parts, src, seq_cap, ctg_seg, segs, k, min_match_len, line_length, names, name_off, d_text, text_cap, dev=True)
         self._chk(rc_)
         return n
 

@@ -28,6 +28,7 @@
 #include "fasta_out_kernels.hip"
 #include "zstd_kernels.hip"
 #include "zstd_decode_kernels.hip"
+#include "parts_unpack_kernels.hip"
 
 using namespace agc;
 
@@ -163,6 +164,7 @@ struct agc_hip_ctx {
         DevBuf d_dec_enc, d_dec_jobs, d_dec_res, d_dec_out; // agc_hip_lz_decode_batch*: the deltas, their descriptors, lengths + status, the symbols
         DevBuf d_fa_sym, d_fa_copy, d_fa_plan, d_fa_text;   // agc_hip_sample_fasta*: the sample's symbols, the copy jobs, the text plan, the text
         DevBuf d_zd_src, d_zd_jobs, d_zd_status, d_zd_ws, d_zd_out; // agc_hip_zstd_decode_batch*: the frames, their descriptors, their statuses, the literals workspaces, the bytes
+        DevBuf d_pu_dec, d_pu_jobs, d_pu_res, d_pu_wjobs, d_pu_out; // agc_hip_parts_unpack*: the decoded parts, their descriptors, infos + end offsets, the write jobs, the final bytes
     } rd;
 
     PackTemp pk1;        // byte-input entry points on the first stream

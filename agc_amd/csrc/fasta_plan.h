@@ -86,6 +86,30 @@ SampleLayout<DJ, CJ> lay_out_sample(uint32_t n_ctg, const uint64_t *h_ctg_seg, c
     return Y;
 }
 
+// The text's size alone, for a caller that must know it before it has what lay_out_sample asks for (agc_hip_sample_fasta_parts:
+// before the parts are unpacked): length(s) = segment s's symbols.  The same arithmetic, so the same number as SampleLayout::text;
+// false: the ranges or name offsets do not ascend from 0.
+template <class Length>
+bool plan_text_bytes(uint32_t n_ctg, const uint64_t *h_ctg_seg, uint32_t k, uint32_t line_length, const uint64_t *h_name_off, Length length, uint64_t &text)
+{
+    const uint64_t n_seg = h_ctg_seg[n_ctg];
+    bool ascending = h_ctg_seg[0] == 0 && n_seg <= 0xFFFFFFFFull;
+    for (uint32_t ci = 0; ci < n_ctg; ++ci)
+        ascending = ascending && h_ctg_seg[ci] <= h_ctg_seg[ci + 1] && h_ctg_seg[ci + 1] <= n_seg && h_name_off[ci] <= h_name_off[ci + 1];
+    text = 0;
+    if (!ascending)
+        return false;
+    for (uint32_t ci = 0; ci < n_ctg; ++ci) {
+        uint64_t pos = 0;
+        for (uint64_t s = h_ctg_seg[ci]; s < h_ctg_seg[ci + 1]; ++s) {
+            const uint32_t sk = s == h_ctg_seg[ci] ? 0 : k, len = length(s);
+            pos += len >= sk ? len - sk : 0;
+        }
+        text += fo::contig_text_bytes(h_name_off[ci + 1] - h_name_off[ci], pos, line_length);
+    }
+    return true;
+}
+
 // the text kernel's arrays in one block (one upload): the 64-bit arrays, the 32-bit one, the names; every member but `bytes` is
 // the offset of that array of fo::PlanT in it
 struct PlanBlock {

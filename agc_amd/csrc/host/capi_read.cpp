@@ -15,6 +15,10 @@ struct agc_plan_t {
     agc::SamplePlan p;
 };
 
+struct agc_parts_t {
+    agc::SampleParts p;
+};
+
 static char **vec2list(const std::vector<std::string> &v)
 {
     char **list = (char **)malloc(sizeof(char *) * (v.size() + 1));
@@ -203,6 +207,53 @@ int agc_plan_fields(const agc_plan_t *plan, agc_plan_view *out)
 int agc_plan_destroy(agc_plan_t *plan)
 {
     delete plan;
+    return 0;
+}
+
+agc_parts_t *agc_get_sample_parts(const agc_t *agc, const char *sample, const uint32_t *have_groups, uint64_t n_have)
+{
+    if (!agc || !sample || (n_have && !have_groups))
+        return nullptr;
+    agc_parts_t *pt = new agc_parts_t;
+    if (!agc->f.GetSampleParts(sample, have_groups, (size_t)n_have, pt->p)) {
+        delete pt;
+        return nullptr;
+    }
+    return pt;
+}
+
+int agc_parts_fields(const agc_parts_t *parts, agc_parts_view *out)
+{
+    if (!parts || !out)
+        return -1;
+    const agc::SampleParts &p = parts->p;
+    out->n_ctg = p.ctg_seg.size() - 1;
+    out->n_seg = p.kind.size();
+    out->n_parts = p.part_off.size();
+    out->src_bytes = p.src_bytes;
+    out->src = p.src;
+    out->names = (const char *)p.names.data();
+    out->name_off = p.name_off.data();
+    out->ctg_seg = p.ctg_seg.data();
+    out->group_id = p.group_id.data();
+    out->in_group_id = p.in_group_id.data();
+    out->rc = p.rc.data();
+    out->length = p.length.data();
+    out->kind = p.kind.data();
+    out->seg_part = p.part.data();
+    out->seg_index = p.index.data();
+    out->part_off = p.part_off.data();
+    out->part_bytes = p.part_bytes.data();
+    out->part_coding = p.part_coding.data();
+    out->part_content = p.part_content.data();
+    out->part_group = p.part_group.data();
+    out->part_no = p.part_no.data();
+    return 0;
+}
+
+int agc_parts_destroy(agc_parts_t *parts)
+{
+    delete parts;
     return 0;
 }
 }

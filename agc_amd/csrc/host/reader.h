@@ -29,6 +29,23 @@ struct SamplePlan {
     std::vector<uint8_t> ref_bytes;
 };
 
+// What a device needs to write a sample's FASTA text from the archive's own bytes (GetSampleParts): the contigs and segments of
+// SamplePlan, and the distinct stored parts the sample touches, as they are stored -- nothing is decoded, no cache is filled.
+struct SampleParts {
+    enum Coding : uint32_t { STORED = 0, ZSTD = 1 };                // archive metadata 0: the bytes as they are; otherwise one zstd frame
+    enum Content : uint32_t { PACK = 0, REF_BYTES = 1, REF_TUPLES = 2 }; // sequences each followed by 0xFF; a reference as symbol bytes; as tuples
+    std::vector<uint8_t> names;
+    std::vector<uint64_t> name_off, ctg_seg; // as in SamplePlan
+    // per segment; length: the collection's raw_length; part / index: RAW, DELTA -- sequence `index` of the pack parts[part]
+    std::vector<uint32_t> group_id, in_group_id, rc, length, kind, part, index;
+    // per part: its bytes are src[off, off + n_bytes) -- a zstd part without the marker byte behind its frame; group: the stream's group;
+    // no: a pack's number in its stream (0 for a reference).  The references come first, ascending by group, then the packs
+    std::vector<uint64_t> part_off;
+    std::vector<uint32_t> part_bytes, part_coding, part_content, part_group, part_no;
+    const uint8_t *src = nullptr; // the archive's bytes (mapped where that is possible): valid until the file is closed
+    uint64_t src_bytes = 0;
+};
+
 class CAGCFile {
     struct Impl;
     std::unique_ptr<Impl> p;
@@ -60,6 +77,10 @@ public:
     bool WriteSampleFasta(const std::string &sample, FILE *f, uint32_t line_length = 80) const;
     // the plan of a whole sample (see SamplePlan); false: unknown sample or an unreadable part
     bool GetSamplePlan(const std::string &sample, SamplePlan &plan) const;
+    // the stored parts of a whole sample (see SampleParts): pack idx / pack_cardinality of x<group>d for every RAW and DELTA segment,
+    // part 0 of x<group>r for every group >= 16 the sample touches that is not among have_groups; false: unknown sample, a part the
+    // archive does not hold
+    bool GetSampleParts(const std::string &sample, const uint32_t *have_groups, size_t n_have, SampleParts &parts) const;
     // one `agc getctg` query -- contig[@sample][:from-to] (agc_decompressor_lib.h:127-130) -- as FASTA text;
     // the header is the full contig name (+ ":from-to" when a range was given), core/agc_decompressor.cpp:478-567
     bool GetContigFasta(const std::string &query, std::string &out, uint32_t line_length, std::string &err) const;

@@ -1,7 +1,11 @@
 // read_api.hip -- the read path of include/agc_hip.h on the context's first stream: agc_hip_zstd_decode_batch (frames -> bytes),
-// agc_hip_lz_decode_batch (deltas -> symbols) and agc_hip_sample_fasta (a sample's plan -> its FASTA text), each with its _dev twin.
-// The three are built from the stages below; the sample's host arithmetic is fasta_plan.h.  Included by api.hip behind the create
-// path (uses its context and helpers; the kernels are lz_decode_kernels.hip, fasta_out_kernels.hip, zstd_decode_kernels.hip).
+// agc_hip_lz_decode_batch (deltas -> symbols), agc_hip_sample_fasta (a sample's plan -> its FASTA text), agc_hip_parts_unpack
+// (archive parts -> packs cut into sequences, references as symbols) and agc_hip_sample_fasta_parts (a sample's archive parts -> its
+// FASTA text), each with its _dev twin.  The five are built from the stages below; the sample's host arithmetic is fasta_plan.h.
+// Included by api.hip behind the create path (uses its context and helpers; the kernels are lz_decode_kernels.hip,
+// fasta_out_kernels.hip, zstd_decode_kernels.hip, parts_unpack_kernels.hip).
+#include <map>
+
 #include "fasta_plan.h"
 
 namespace {
@@ -45,9 +49,9 @@ int hand_back(agc_hip_ctx *c, uint8_t *h_out, const uint8_t *d_out, uint64_t byt
     return AGC_HIP_OK;
 }
 
-// The scan stage: the jobs go up, lz_decode_scan_kernel walks every delta (they lie in d_dec_enc already, a wave per delta) and the
+// The scan stage: the jobs go up, lz_decode_scan_kernel walks every delta (they lie in d_enc already, a wave per delta) and the
 // host waits for each one's length and status.
-int decode_scan(agc_hip_ctx *c, const std::vector<DecodeJob> &jobs, std::vector<DecodeResult> &res)
+int decode_scan(agc_hip_ctx *c, const std::vector<DecodeJob> &jobs, const uint8_t *d_enc, std::vector<DecodeResult> &res)
 {
     const uint32_t n = (uint32_t)jobs.size();
     CHK(ensure(c, c->rd.d_dec_jobs, (size_t)n * sizeof(DecodeJob)));
@@ -56,7 +60,7 @@ int decode_scan(agc_hip_ctx *c, const std::vector<DecodeJob> &jobs, std::vector<
     {
         KTimer t(c, AGC_HIP_K_DECODE_SCAN);
         hipLaunchKernelGGL(lz_decode_scan_kernel, dim3((n + 3) / 4), dim3(4 * WAVE), 0, c->stream, (const RefDesc *)c->d_refs.p, (const DecodeJob *)c->rd.d_dec_jobs.p, n,
-                           (const uint8_t *)c->rd.d_dec_enc.p, (DecodeResult *)c->rd.d_dec_res.p);
+                           d_enc, (DecodeResult *)c->rd.d_dec_res.p);
     }
     HIPCHK(c, hipGetLastError());
     res.resize(n);
@@ -66,16 +70,275 @@ int decode_scan(agc_hip_ctx *c, const std::vector<DecodeJob> &jobs, std::vector<
 }
 
 // The write stage: lz_decode_write_kernel decodes the n jobs in d_dec_jobs -- scanned, and now saying where each delta's symbols go
-// -- into d_out.
-int decode_write(agc_hip_ctx *c, uint32_t n, uint8_t *d_out)
+// -- out of d_enc into d_out.
+int decode_write(agc_hip_ctx *c, uint32_t n, const uint8_t *d_enc, uint8_t *d_out)
 {
     {
         KTimer t(c, AGC_HIP_K_DECODE_WRITE);
         hipLaunchKernelGGL(lz_decode_write_kernel, dim3((n + 3) / 4), dim3(4 * WAVE), 0, c->stream, (const RefDesc *)c->d_refs.p, (const DecodeJob *)c->rd.d_dec_jobs.p, n,
-                           (const uint8_t *)c->rd.d_dec_enc.p, d_out);
+                           d_enc, d_out);
     }
     HIPCHK(c, hipGetLastError());
     return AGC_HIP_OK;
+}
+
+// how fasta_text_kernel is launched for a text of `text` bytes at d_text (nullptr: the context's buffer, which is aligned)
+struct TextLaunch {
+    uint32_t a;
+    uint64_t n_chunks, blocks;
+};
+
+int text_launch(agc_hip_ctx *c, const uint8_t *d_text, uint64_t text, TextLaunch &T)
+{
+    T.a = d_text ? (uint32_t)((uintptr_t)d_text & (fo::CHUNK - 1)) : 0;
+    T.n_chunks = fo::chunk_count(T.a, text);
+    T.blocks = (T.n_chunks + 255) / 256;
+    if (T.blocks > 0x7FFFFFFFull) {
+        c->err = "sample_fasta: a text of " + std::to_string(text) + " bytes is more than one launch writes";
+        return AGC_HIP_EINVAL;
+    }
+    return AGC_HIP_OK;
+}
+
+using SampleLayout = fp::SampleLayout<DecodeJob, CopyJob>;
+
+// The sample stage: everything behind a sample's layout Y, its deltas and raw symbols in d_bytes already.  The deltas are checked by
+// the scan stage, against the length the plan declares, before anything is written: the write stage and segment_copy_kernel then lay
+// the segments out in the symbol buffer, fasta_text_kernel writes the text.
+int write_sample(agc_hip_ctx *c, const SampleLayout &Y, const uint8_t *d_bytes, uint32_t n_ctg, const uint64_t *h_ctg_seg, const char *h_names,
+                 const uint64_t *h_name_off, uint32_t line_length, uint8_t *h_text, uint8_t *d_text, const TextLaunch &T)
+{
+    CHK(upload_refs(c));
+    const uint32_t n_dj = (uint32_t)Y.dj.size(), n_cj = (uint32_t)Y.cj.size();
+    if (n_dj) {
+        std::vector<DecodeResult> res;
+        CHK(decode_scan(c, Y.dj, d_bytes, res));
+        for (uint32_t i = 0; i < n_dj; ++i)
+            if (res[i].status != lzd::OK || res[i].len != Y.dj[i].out_len) {
+                c->err = "sample_fasta: segment " + std::to_string(Y.dj_seg[i]) +
+                         (res[i].status != lzd::OK ? " has a malformed delta" : " decodes to " + std::to_string(res[i].len) + " symbols, its length says " + std::to_string(Y.dj[i].out_len));
+                return AGC_HIP_EINVAL;
+            }
+    }
+    // every segment has passed: from here on things are written
+    CHK(ensure(c, c->rd.d_fa_sym, Y.sym_total + 64));
+    uint8_t *d_sym = c->rd.d_fa_sym.as<uint8_t>();
+    if (n_dj)
+        CHK(decode_write(c, n_dj, d_bytes, d_sym));
+    if (n_cj) {
+        CHK(ensure(c, c->rd.d_fa_copy, (size_t)n_cj * sizeof(CopyJob)));
+        CHK(upload(c, c->rd.d_fa_copy.p, Y.cj.data(), (size_t)n_cj * sizeof(CopyJob), c->stream));
+        KTimer t(c, AGC_HIP_K_FASTA_OUT);
+        hipLaunchKernelGGL(segment_copy_kernel, dim3((n_cj + 3) / 4), dim3(4 * WAVE), 0, c->stream, (const RefDesc *)c->d_refs.p, (const CopyJob *)c->rd.d_fa_copy.p, n_cj,
+                           d_bytes, d_sym); // a wave per segment
+    }
+    HIPCHK(c, hipGetLastError());
+    const fp::PlanBlock B = fp::pack_text_plan(Y, n_ctg, h_ctg_seg, h_names, h_name_off);
+    CHK(ensure(c, c->rd.d_fa_plan, B.bytes.size() + 64));
+    CHK(upload(c, c->rd.d_fa_plan.p, B.bytes.data(), B.bytes.size(), c->stream));
+    CHK(output_buffer(c, d_text, c->rd.d_fa_text, Y.text));
+    const uint8_t *pl = c->rd.d_fa_plan.as<uint8_t>();
+    const TextPlan P = {(g_u64 *)(pl + B.ctg_text), (g_u64 *)(pl + B.ctg_seg), (g_u64 *)(pl + B.ctg_sym), (g_u64 *)(pl + B.name_off), (g_u8 *)(pl + B.names),
+                        (g_u64 *)(pl + B.seg_start), (g_u64 *)(pl + B.seg_off), (g_u32 *)(pl + B.skip), (g_u8 *)d_sym, n_ctg, line_length};
+    {
+        KTimer t(c, AGC_HIP_K_FASTA_OUT);
+        hipLaunchKernelGGL(fasta_text_kernel, dim3((uint32_t)T.blocks), dim3(256), 0, c->stream, P, d_text, T.a, Y.text, T.n_chunks);
+    }
+    HIPCHK(c, hipGetLastError());
+    return hand_back(c, h_text, d_text, Y.text);
+}
+
+// The zstd stage: the frames lie in d_src already, their headers read by the host.  zstd_decode_kernel gives every job a wave, its
+// slice of d_out and its slice of the literals workspace (ws_tot bytes in all); a job whose header the host refused only hands its
+// status on.  The statuses stay in d_zd_status, one per job.
+int zstd_decode_stage(agc_hip_ctx *c, const std::vector<ZDecJob> &jobs, uint64_t ws_tot, const uint8_t *d_src, uint8_t *d_out)
+{
+    const uint32_t n = (uint32_t)jobs.size();
+    CHK(ensure(c, c->rd.d_zd_jobs, (size_t)n * sizeof(ZDecJob)));
+    CHK(ensure(c, c->rd.d_zd_status, (size_t)n * sizeof(uint32_t)));
+    CHK(ensure(c, c->rd.d_zd_ws, ws_tot + 64));
+    CHK(upload(c, c->rd.d_zd_jobs.p, jobs.data(), (size_t)n * sizeof(ZDecJob), c->stream));
+    {
+        KTimer t(c, AGC_HIP_K_ZSTD_DECODE);
+        hipLaunchKernelGGL(zstd_decode_kernel, dim3(n), dim3(WAVE), 0, c->stream, (const ZDecJob *)c->rd.d_zd_jobs.p, n, d_src, d_out, (uint8_t *)c->rd.d_zd_ws.p,
+                           (uint32_t *)c->rd.d_zd_status.p); // a wave per frame
+    }
+    HIPCHK(c, hipGetLastError());
+    return AGC_HIP_OK;
+}
+
+// one frame's job from its header: where it lies in the source, where its bytes and its literals workspace (min(content size,
+// 128 KiB): what a block's literals can need) begin
+ZDecJob zstd_job(const zs::dec::FrameHeader &h, uint64_t src_off, uint64_t len, uint64_t out_off, uint64_t &ws_tot)
+{
+    const uint32_t ws_len = (std::min(h.contentSize, zs::BLOCKSIZE_MAX) + 15u) & ~15u;
+    const ZDecJob jb = {src_off, out_off, ws_tot, (uint32_t)len, h.contentSize, ws_len, h.status};
+    ws_tot += ws_len;
+    return jb;
+}
+
+// ---- the parts stage -------------------------------------------------------------------------------------------------------------
+// what it leaves: every part's decoded bytes in d_pu_dec (jobs[i].dec_off, 16-byte aligned, the STORED parts in front), and what the
+// device found out about them
+struct PartsState {
+    std::vector<PartJob> jobs;
+    std::vector<PartInfo> info;    // status; a pack's count; a reference's nb and symbols
+    std::vector<uint32_t> seq_end; // jobs[i].seq_row * seq_cap + q: where sequence q of pack i ends
+    uint32_t seq_cap = 0;
+    uint64_t dec_bytes = 0;
+
+    uint32_t status(uint32_t i) const { return info[i].status; }
+    // sequence q < min(count, seq_cap) of pack i, as bytes of d_pu_dec
+    void sequence(uint32_t i, uint32_t q, uint64_t &off, uint32_t &n) const
+    {
+        const uint32_t *row = seq_end.data() + (size_t)jobs[i].seq_row * seq_cap;
+        const uint32_t begin = q ? row[q - 1] + 1 : 0;
+        off = jobs[i].dec_off + begin;
+        n = row[q] - begin;
+    }
+};
+
+// the parts as arguments: inside the source, of a known coding and content
+int parts_check(agc_hip_ctx *c, const char *call, uint32_t n, const agc_hip_part *h_parts, uint64_t src_bytes)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        const agc_hip_part &p = h_parts[i];
+        const char *why = p.off > src_bytes || p.n_bytes > src_bytes - p.off ? "lies outside the source buffer"
+                          : p.coding > AGC_HIP_PART_ZSTD                    ? "has an unknown coding"
+                          : p.content > AGC_HIP_PART_REF_TUPLES             ? "has an unknown content"
+                                                                            : nullptr;
+        if (why) {
+            c->err = std::string(call) + ": part " + std::to_string(i) + " " + why;
+            return AGC_HIP_EINVAL;
+        }
+    }
+    return AGC_HIP_OK;
+}
+
+// The parts stage (n >= 1 checked parts): the ZSTD parts through the zstd stage into d_pu_dec, the STORED ones uploaded beside them;
+// pack_index_kernel cuts the packs (a wave each), tuples_size_kernel reads the references' shapes; infos and end offsets come back
+// in one copy, which the host waits for.
+int parts_decode_index(agc_hip_ctx *c, uint32_t n, const agc_hip_part *h_parts, const uint8_t *h_src, uint32_t seq_cap, PartsState &S)
+{
+    S.jobs.assign(n, PartJob());
+    S.seq_cap = seq_cap;
+    std::vector<uint32_t> ids(n); // the packs' part numbers from the front, the references' from the back
+    uint32_t n_packs = 0, n_refs = 0, n_live = 0;
+    uint64_t tot = 0, ws_tot = 0;
+    std::vector<uint8_t> stored, frames;
+    std::vector<ZDecJob> zj;
+    auto align = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
+    for (uint32_t i = 0; i < n; ++i) {
+        const agc_hip_part &p = h_parts[i];
+        PartJob &j = S.jobs[i];
+        j.content = p.content;
+        j.zd_slot = ~0u;
+        if (p.content == AGC_HIP_PART_PACK) {
+            j.seq_row = n_packs;
+            ids[n_packs++] = i;
+        } else
+            ids[n - ++n_refs] = i;
+        if (p.coding == AGC_HIP_PART_STORED) {
+            j.dec_off = tot;
+            j.dec_len = p.n_bytes;
+            tot += align(p.n_bytes);
+            stored.resize(tot);
+            if (p.n_bytes)
+                std::memcpy(stored.data() + j.dec_off, h_src + p.off, p.n_bytes);
+        }
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+        const agc_hip_part &p = h_parts[i];
+        if (p.coding != AGC_HIP_PART_ZSTD)
+            continue;
+        PartJob &j = S.jobs[i];
+        const zs::dec::FrameHeader h = zs::dec::parseFrameHeader(h_src + p.off, p.n_bytes);
+        j.status = h.status;
+        j.dec_off = tot;
+        j.dec_len = h.status == zs::dec::OK ? h.contentSize : 0;
+        j.zd_slot = (uint32_t)zj.size();
+        zj.push_back(zstd_job(h, frames.size(), p.n_bytes, tot, ws_tot));
+        frames.insert(frames.end(), h_src + p.off, h_src + p.off + p.n_bytes);
+        tot += align(j.dec_len);
+        n_live += h.status == zs::dec::OK;
+    }
+    if (!n_live) // (every header refused, or no ZSTD part: the zstd stage does not run and leaves no status to read)
+        for (PartJob &j : S.jobs)
+            j.zd_slot = ~0u;
+    S.dec_bytes = tot;
+    CHK(ensure(c, c->rd.d_pu_dec, tot + 64));
+    uint8_t *d_dec = c->rd.d_pu_dec.as<uint8_t>();
+    if (!stored.empty())
+        CHK(upload(c, d_dec, stored.data(), stored.size(), c->stream));
+    if (n_live) {
+        CHK(ensure(c, c->rd.d_zd_src, frames.size() + 64));
+        CHK(upload(c, c->rd.d_zd_src.p, frames.data(), frames.size(), c->stream));
+        CHK(zstd_decode_stage(c, zj, ws_tot, c->rd.d_zd_src.as<uint8_t>(), d_dec));
+    }
+    // descriptors and part numbers in one block up, infos and end offsets in one block down
+    const size_t jobs_bytes = (size_t)n * sizeof(PartJob), info_bytes = (size_t)n * sizeof(PartInfo), ends = (size_t)n_packs * seq_cap;
+    std::vector<uint8_t> up(jobs_bytes + (size_t)n * 4), down(info_bytes + ends * 4);
+    std::memcpy(up.data(), S.jobs.data(), jobs_bytes);
+    std::memcpy(up.data() + jobs_bytes, ids.data(), (size_t)n * 4);
+    CHK(ensure(c, c->rd.d_pu_jobs, up.size()));
+    CHK(ensure(c, c->rd.d_pu_res, down.size() + 64));
+    CHK(upload(c, c->rd.d_pu_jobs.p, up.data(), up.size(), c->stream));
+    const PartJob *d_jobs = c->rd.d_pu_jobs.as<PartJob>();
+    const uint32_t *d_ids = (const uint32_t *)(c->rd.d_pu_jobs.as<uint8_t>() + jobs_bytes);
+    PartInfo *d_info = c->rd.d_pu_res.as<PartInfo>();
+    uint32_t *d_ends = (uint32_t *)(c->rd.d_pu_res.as<uint8_t>() + info_bytes);
+    const uint32_t *d_zst = (const uint32_t *)c->rd.d_zd_status.p; // (read only through a zd_slot the zstd stage filled)
+    if (n_packs) {
+        KTimer t(c, AGC_HIP_K_PARTS_UNPACK);
+        hipLaunchKernelGGL(pack_index_kernel, dim3((n_packs + 3) / 4), dim3(4 * WAVE), 0, c->stream, d_jobs, d_ids, n_packs, (const uint8_t *)d_dec, d_zst, seq_cap, d_ends,
+                           d_info); // a wave per pack
+    }
+    if (n_refs) {
+        KTimer t(c, AGC_HIP_K_PARTS_UNPACK);
+        hipLaunchKernelGGL(tuples_size_kernel, dim3((n_refs + 255) / 256), dim3(256), 0, c->stream, d_jobs, d_ids + n_packs, n_refs, (const uint8_t *)d_dec, d_zst, d_info);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(down.data(), c->rd.d_pu_res.p, down.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    S.info.resize(n);
+    std::memcpy(S.info.data(), down.data(), info_bytes);
+    S.seq_end.resize(ends);
+    if (ends)
+        std::memcpy(S.seq_end.data(), down.data() + info_bytes, ends * 4);
+    return AGC_HIP_OK;
+}
+
+// The unpack-write stage: tuples_unpack_kernel fills out[out_off, out_off + n) of every job -- symbols out of a tuple stream, or
+// bytes as they are -- from d_pu_dec; the jobs (each with n >= 1) get their share of the launch's chunks here.
+int unpack_write(agc_hip_ctx *c, std::vector<UnpackJob> &jobs, uint8_t *d_out)
+{
+    if (jobs.empty())
+        return AGC_HIP_OK;
+    uint64_t n_chunks = 0;
+    for (UnpackJob &j : jobs) {
+        j.a = (uint32_t)((uintptr_t)(d_out + j.out_off) & (fo::CHUNK - 1));
+        j.first_chunk = n_chunks;
+        n_chunks += fo::chunk_count(j.a, j.n);
+    }
+    const uint64_t blocks = (n_chunks + 255) / 256;
+    if (blocks > 0x7FFFFFFFull) {
+        c->err = "parts_unpack: " + std::to_string(n_chunks) + " chunks of 16 bytes are more than one launch writes";
+        return AGC_HIP_EINVAL;
+    }
+    CHK(ensure(c, c->rd.d_pu_wjobs, jobs.size() * sizeof(UnpackJob)));
+    CHK(upload(c, c->rd.d_pu_wjobs.p, jobs.data(), jobs.size() * sizeof(UnpackJob), c->stream));
+    {
+        KTimer t(c, AGC_HIP_K_PARTS_UNPACK);
+        hipLaunchKernelGGL(tuples_unpack_kernel, dim3((uint32_t)blocks), dim3(256), 0, c->stream, (const UnpackJob *)c->rd.d_pu_wjobs.p, (uint32_t)jobs.size(), n_chunks,
+                           (const uint8_t *)c->rd.d_pu_dec.p, d_out);
+    }
+    HIPCHK(c, hipGetLastError());
+    return AGC_HIP_OK;
+}
+
+const char *part_refusal(uint32_t status)
+{
+    return status == pu::ZSTD_UNSUPPORTED ? "an unsupported zstd frame (status 1)" : status == pu::ZSTD_MALFORMED ? "a malformed zstd frame (status 2)" : "a malformed tuple stream (status 3)";
 }
 
 } // namespace
@@ -108,7 +371,7 @@ static int lz_decode_impl(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, con
     if (enc_bytes)
         CHK(upload(c, c->rd.d_dec_enc.p, h_enc + e0, enc_bytes, c->stream));
     std::vector<DecodeResult> res;
-    CHK(decode_scan(c, jobs, res));
+    CHK(decode_scan(c, jobs, c->rd.d_dec_enc.as<uint8_t>(), res));
     for (uint32_t i = 0; i < n; ++i)
         if (res[i].status != lzd::OK) {
             static const char *why[] = {"", "a truncated or malformed token", "'!' at or past the end of the reference", "a match outside the reference",
@@ -129,7 +392,7 @@ static int lz_decode_impl(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, con
         return AGC_HIP_OK;
     CHK(output_buffer(c, d_out, c->rd.d_dec_out, tot));
     CHK(upload(c, c->rd.d_dec_jobs.p, jobs.data(), (size_t)n * sizeof(DecodeJob), c->stream)); // (now with where each delta's symbols go)
-    CHK(decode_write(c, n, d_out));
+    CHK(decode_write(c, n, c->rd.d_dec_enc.as<uint8_t>(), d_out));
     return hand_back(c, h_out, d_out, tot);
 }
 
@@ -154,59 +417,17 @@ static int sample_fasta_impl(agc_hip_ctx *c, uint32_t n_ctg, const uint64_t *h_c
         return Y.code;
     }
     CHK(capacity_holds(c, "sample_fasta", "text", text_cap, Y.text));
-    const uint32_t a = d_text ? (uint32_t)((uintptr_t)d_text & (fo::CHUNK - 1)) : 0;
-    const uint64_t n_chunks = fo::chunk_count(a, Y.text), text_blocks = (n_chunks + 255) / 256;
-    if (text_blocks > 0x7FFFFFFFull) {
-        c->err = "sample_fasta: a text of " + std::to_string(Y.text) + " bytes is more than one launch writes";
-        return AGC_HIP_EINVAL;
-    }
+    TextLaunch T;
+    CHK(text_launch(c, d_text, Y.text, T));
     HIPCHK(c, hipSetDevice(c->device));
-    CHK(upload_refs(c));
     CHK(ensure(c, c->rd.d_dec_enc, n_bytes + 64));
     if (n_bytes)
         CHK(upload(c, c->rd.d_dec_enc.p, h_bytes, n_bytes, c->stream));
-    const uint32_t n_dj = (uint32_t)Y.dj.size(), n_cj = (uint32_t)Y.cj.size();
-    if (n_dj) {
-        std::vector<DecodeResult> res;
-        CHK(decode_scan(c, Y.dj, res));
-        for (uint32_t i = 0; i < n_dj; ++i)
-            if (res[i].status != lzd::OK || res[i].len != Y.dj[i].out_len) {
-                c->err = "sample_fasta: segment " + std::to_string(Y.dj_seg[i]) +
-                         (res[i].status != lzd::OK ? " has a malformed delta" : " decodes to " + std::to_string(res[i].len) + " symbols, its length says " + std::to_string(Y.dj[i].out_len));
-                return AGC_HIP_EINVAL;
-            }
-    }
-    // every segment has passed: from here on things are written
-    CHK(ensure(c, c->rd.d_fa_sym, Y.sym_total + 64));
-    uint8_t *d_sym = c->rd.d_fa_sym.as<uint8_t>();
-    if (n_dj)
-        CHK(decode_write(c, n_dj, d_sym));
-    if (n_cj) {
-        CHK(ensure(c, c->rd.d_fa_copy, (size_t)n_cj * sizeof(CopyJob)));
-        CHK(upload(c, c->rd.d_fa_copy.p, Y.cj.data(), (size_t)n_cj * sizeof(CopyJob), c->stream));
-        KTimer t(c, AGC_HIP_K_FASTA_OUT);
-        hipLaunchKernelGGL(segment_copy_kernel, dim3((n_cj + 3) / 4), dim3(4 * WAVE), 0, c->stream, (const RefDesc *)c->d_refs.p, (const CopyJob *)c->rd.d_fa_copy.p, n_cj,
-                           (const uint8_t *)c->rd.d_dec_enc.p, d_sym); // a wave per segment
-    }
-    HIPCHK(c, hipGetLastError());
-    const fp::PlanBlock B = fp::pack_text_plan(Y, n_ctg, h_ctg_seg, h_names, h_name_off);
-    CHK(ensure(c, c->rd.d_fa_plan, B.bytes.size() + 64));
-    CHK(upload(c, c->rd.d_fa_plan.p, B.bytes.data(), B.bytes.size(), c->stream));
-    CHK(output_buffer(c, d_text, c->rd.d_fa_text, Y.text));
-    const uint8_t *pl = c->rd.d_fa_plan.as<uint8_t>();
-    const TextPlan P = {(g_u64 *)(pl + B.ctg_text), (g_u64 *)(pl + B.ctg_seg), (g_u64 *)(pl + B.ctg_sym), (g_u64 *)(pl + B.name_off), (g_u8 *)(pl + B.names),
-                        (g_u64 *)(pl + B.seg_start), (g_u64 *)(pl + B.seg_off), (g_u32 *)(pl + B.skip), (g_u8 *)d_sym, n_ctg, line_length};
-    {
-        KTimer t(c, AGC_HIP_K_FASTA_OUT);
-        hipLaunchKernelGGL(fasta_text_kernel, dim3((uint32_t)text_blocks), dim3(256), 0, c->stream, P, d_text, a, Y.text, n_chunks);
-    }
-    HIPCHK(c, hipGetLastError());
-    return hand_back(c, h_text, d_text, Y.text);
+    return write_sample(c, Y, c->rd.d_dec_enc.as<uint8_t>(), n_ctg, h_ctg_seg, h_names, h_name_off, line_length, h_text, d_text, T);
 }
 
 // The zstd decode.  The host reads every frame header: that sizes the output, and a frame whose header is refused never reaches the
-// decoder.  zstd_decode_kernel then gives every other frame a wave, its slice of the output and its slice of the literals
-// workspace (min(content size, 128 KiB): what a block's literals can need).
+// decoder.  The zstd stage then gives every other frame a wave, its slice of the output and its slice of the literals workspace.
 static int zstd_decode_impl(agc_hip_ctx *c, uint32_t n, const uint8_t *h_src, const uint64_t *h_src_off, uint8_t *h_out, uint8_t *d_out, uint64_t out_cap,
                             uint64_t *h_out_off, uint32_t *h_status)
 {
@@ -224,11 +445,9 @@ static int zstd_decode_impl(agc_hip_ctx *c, uint32_t n, const uint8_t *h_src, co
     for (uint32_t i = 0; i < n; ++i) {
         const uint64_t len = h_src_off[i + 1] - h_src_off[i];
         const zs::dec::FrameHeader h = zs::dec::parseFrameHeader(h_src + h_src_off[i], len);
-        const uint32_t ws_len = (std::min(h.contentSize, zs::BLOCKSIZE_MAX) + 15u) & ~15u;
-        jobs[i] = {h_src_off[i] - s0, tot, ws_tot, (uint32_t)len, h.contentSize, ws_len, h.status};
+        jobs[i] = zstd_job(h, h_src_off[i] - s0, len, tot, ws_tot);
         h_out_off[i] = tot;
         tot += h.contentSize;
-        ws_tot += ws_len;
         n_live += h.status == zs::dec::OK;
         if (h_status)
             h_status[i] = h.status;
@@ -239,19 +458,10 @@ static int zstd_decode_impl(agc_hip_ctx *c, uint32_t n, const uint8_t *h_src, co
     if (n_live) {
         HIPCHK(c, hipSetDevice(c->device));
         CHK(ensure(c, c->rd.d_zd_src, src_bytes + 64));
-        CHK(ensure(c, c->rd.d_zd_jobs, (size_t)n * sizeof(ZDecJob)));
-        CHK(ensure(c, c->rd.d_zd_status, (size_t)n * sizeof(uint32_t)));
-        CHK(ensure(c, c->rd.d_zd_ws, ws_tot + 64));
         // (an output of 0 bytes: the context's buffer stands in for a d_out the caller did not have to give)
         CHK(output_buffer(c, d_out, c->rd.d_zd_out, tot));
         CHK(upload(c, c->rd.d_zd_src.p, h_src + s0, src_bytes, c->stream));
-        CHK(upload(c, c->rd.d_zd_jobs.p, jobs.data(), (size_t)n * sizeof(ZDecJob), c->stream));
-        {
-            KTimer t(c, AGC_HIP_K_ZSTD_DECODE);
-            hipLaunchKernelGGL(zstd_decode_kernel, dim3(n), dim3(WAVE), 0, c->stream, (const ZDecJob *)c->rd.d_zd_jobs.p, n, (const uint8_t *)c->rd.d_zd_src.p, d_out,
-                               (uint8_t *)c->rd.d_zd_ws.p, (uint32_t *)c->rd.d_zd_status.p); // a wave per frame
-        }
-        HIPCHK(c, hipGetLastError());
+        CHK(zstd_decode_stage(c, jobs, ws_tot, c->rd.d_zd_src.as<uint8_t>(), d_out));
         HIPCHK(c, hipMemcpyAsync(status.data(), c->rd.d_zd_status.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         CHK(hand_back(c, h_out, d_out, tot));
     } else
@@ -266,6 +476,168 @@ static int zstd_decode_impl(agc_hip_ctx *c, uint32_t n, const uint8_t *h_src, co
             return AGC_HIP_EINVAL;
         }
     return AGC_HIP_OK;
+}
+
+// The parts of an archive into their final bytes.  The parts stage leaves everything decoded in the context's buffer and the host
+// knowing every size; only then is the caller's capacity looked at and, when it holds, the unpack-write stage fills the output:
+// a pack's and a byte reference's bytes as they are, a tuple reference's symbols.
+static int parts_unpack_impl(agc_hip_ctx *c, uint32_t n, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap, uint8_t *h_out,
+                             uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_off, uint32_t *h_count, uint32_t *h_seq_end, uint32_t *h_status)
+{
+    if (!c || !h_out_off || (n && (!h_parts || !h_count || !h_status || (seq_cap && !h_seq_end) || (src_bytes && !h_src))) || (out_cap && !h_out && !d_out))
+        return AGC_HIP_EINVAL;
+    h_out_off[0] = 0;
+    if (!n)
+        return AGC_HIP_OK;
+    CHK(parts_check(c, "parts_unpack", n, h_parts, src_bytes));
+    HIPCHK(c, hipSetDevice(c->device));
+    PartsState S;
+    CHK(parts_decode_index(c, n, h_parts, h_src, seq_cap, S));
+    std::vector<UnpackJob> wj;
+    uint64_t tot = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const PartJob &j = S.jobs[i];
+        const PartInfo &f = S.info[i];
+        const bool pack = j.content == AGC_HIP_PART_PACK;
+        h_status[i] = f.status;
+        h_out_off[i] = tot;
+        if (f.status != pu::OK)
+            continue;
+        const uint64_t bytes = pack ? j.dec_len : f.n;
+        if (bytes)
+            wj.push_back({j.dec_off, tot, bytes, 0, pack ? 0u : f.count, 0});
+        tot += bytes;
+        if (pack) {
+            h_count[i] = f.count;
+            const uint32_t stored = std::min(f.count, seq_cap);
+            if (stored)
+                std::memcpy(h_seq_end + (size_t)i * seq_cap, S.seq_end.data() + (size_t)j.seq_row * seq_cap, (size_t)stored * 4);
+        }
+    }
+    h_out_off[n] = tot;
+    CHK(capacity_holds(c, "parts_unpack", "output", out_cap, tot));
+    if (tot) {
+        CHK(output_buffer(c, d_out, c->rd.d_pu_out, tot));
+        CHK(unpack_write(c, wj, d_out));
+        CHK(hand_back(c, h_out, d_out, tot));
+    }
+    for (uint32_t i = 0; i < n; ++i)
+        if (h_status[i] != pu::OK) {
+            c->err = "parts_unpack: part " + std::to_string(i) + " is refused: " + part_refusal(h_status[i]);
+            return AGC_HIP_EINVAL;
+        }
+    return AGC_HIP_OK;
+}
+
+// The FASTA text of a sample from its archive parts: the order of events is the contract (include/agc_hip.h).  Everything the host
+// can refuse is refused before the references are registered -- a group registers once, so a call that fails before that leaves the
+// context as it found it; behind the registration only the deltas themselves can still be refused.
+static int sample_fasta_parts_impl(agc_hip_ctx *c, uint32_t n_parts, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap,
+                                   uint32_t n_ctg, const uint64_t *h_ctg_seg, const agc_hip_seg_part *h_seg, uint32_t k, uint32_t min_match_len, uint32_t line_length,
+                                   const char *h_names, const uint64_t *h_name_off, uint8_t *h_text, uint8_t *d_text, uint64_t text_cap, uint64_t *h_text_len)
+{
+    static const char *call = "sample_fasta_parts";
+    if (!c || !h_text_len || (n_ctg && (!h_ctg_seg || !h_name_off || (h_ctg_seg[n_ctg] && !h_seg))) || (n_parts && (!h_parts || (src_bytes && !h_src))) ||
+        (text_cap && !h_text && !d_text))
+        return AGC_HIP_EINVAL;
+    *h_text_len = 0;
+    if (!n_ctg)
+        return AGC_HIP_OK;
+    // 1. the text's size
+    uint64_t text = 0;
+    if (!fp::plan_text_bytes(n_ctg, h_ctg_seg, k, line_length, h_name_off, [h_seg](uint64_t s) { return h_seg[s].length; }, text)) {
+        c->err = std::string(call) + ": the contigs' segment ranges or name offsets do not ascend from 0";
+        return AGC_HIP_EINVAL;
+    }
+    *h_text_len = text;
+    CHK(capacity_holds(c, call, "text", text_cap, text));
+    TextLaunch T;
+    CHK(text_launch(c, d_text, text, T));
+    // 2. the plan against the parts and the context
+    CHK(parts_check(c, call, n_parts, h_parts, src_bytes));
+    auto registered = [c](uint32_t gid) { return gid < c->refs.size() && c->refs[gid].valid; };
+    std::map<uint32_t, uint32_t> new_ref; // group -> its part
+    for (uint32_t i = 0; i < n_parts; ++i)
+        if (h_parts[i].content != AGC_HIP_PART_PACK) {
+            const uint32_t g = h_parts[i].gid;
+            if (registered(g) || !new_ref.emplace(g, i).second) {
+                c->err = std::string(call) + ": part " + std::to_string(i) + " is a reference of group " + std::to_string(g) + ", which " +
+                         (registered(g) ? "is registered already" : "another part is a reference of as well");
+                return AGC_HIP_EINVAL;
+            }
+        }
+    if (!new_ref.empty() && (min_match_len < HASHING_STEP + 4 || min_match_len > 32)) {
+        c->err = std::string(call) + ": a min_match_len of " + std::to_string(min_match_len) + " registers no reference";
+        return AGC_HIP_EINVAL;
+    }
+    const uint64_t n_seg = h_ctg_seg[n_ctg];
+    for (uint64_t s = 0; s < n_seg; ++s) {
+        const agc_hip_seg_part &g = h_seg[s];
+        const char *why = nullptr;
+        int code = AGC_HIP_EINVAL;
+        if (g.kind > AGC_HIP_SEG_DELTA)
+            why = "has an unknown kind";
+        else if (g.kind != AGC_HIP_SEG_RAW && !registered(g.gid) && !new_ref.count(g.gid))
+            why = "names a group that has no registered reference and none among the parts", code = AGC_HIP_ENOREF;
+        else if (g.kind != AGC_HIP_SEG_REF && (g.part >= n_parts || h_parts[g.part].content != AGC_HIP_PART_PACK))
+            why = "names a part that is not a pack of the batch";
+        if (why) {
+            c->err = std::string(call) + ": segment " + std::to_string(s) + " " + why;
+            return code;
+        }
+    }
+    // 3. the parts, unpacked on the device
+    HIPCHK(c, hipSetDevice(c->device));
+    PartsState S;
+    if (n_parts)
+        CHK(parts_decode_index(c, n_parts, h_parts, h_src, seq_cap, S));
+    // 4. what the device found, against the plan; the layout with the new references' sizes -- nothing is registered or written yet
+    for (uint32_t i = 0; i < n_parts; ++i)
+        if (S.status(i) != pu::OK || (h_parts[i].content != AGC_HIP_PART_PACK && S.info[i].n > 0xFFFFFFFFull)) {
+            c->err = std::string(call) + ": part " + std::to_string(i) + " is refused: " + (S.status(i) != pu::OK ? part_refusal(S.status(i)) : "a reference of 2^32 symbols or more");
+            return AGC_HIP_EINVAL;
+        }
+    std::vector<agc_hip_seg_src> seg(n_seg);
+    for (uint64_t s = 0; s < n_seg; ++s) {
+        const agc_hip_seg_part &g = h_seg[s];
+        seg[s] = {g.kind, g.gid, 0, 0, g.length, g.rc, 0};
+        if (g.kind == AGC_HIP_SEG_REF)
+            continue;
+        if (g.index >= S.info[g.part].count || g.index >= seq_cap) {
+            c->err = std::string(call) + ": segment " + std::to_string(s) + " is sequence " + std::to_string(g.index) + " of part " + std::to_string(g.part) + ", which has " +
+                     std::to_string(S.info[g.part].count) + " (at most " + std::to_string(seq_cap) + " are indexed)";
+            return AGC_HIP_EINVAL;
+        }
+        S.sequence(g.part, g.index, seg[s].off, seg[s].n_bytes);
+    }
+    const SampleLayout Y = fp::lay_out_sample<DecodeJob, CopyJob>(n_ctg, h_ctg_seg, seg.data(), S.dec_bytes, k, line_length, h_name_off, [&](uint32_t gid) {
+        const auto it = new_ref.find(gid);
+        return it != new_ref.end() ? (int64_t)S.info[it->second].n : registered(gid) ? (int64_t)c->refs[gid].ref_size : (int64_t)-1;
+    });
+    if (Y.code != AGC_HIP_OK) {
+        c->err = Y.why;
+        return Y.code;
+    }
+    // 5. the new references: their symbols back to back (16-byte aligned) in the context's buffer, registered in one batch from there
+    if (!new_ref.empty()) {
+        std::vector<UnpackJob> wj;
+        std::vector<uint32_t> gid, len;
+        std::vector<uint64_t> off;
+        uint64_t tot = 0;
+        for (const auto &gr : new_ref) {
+            const PartJob &j = S.jobs[gr.second];
+            const PartInfo &f = S.info[gr.second];
+            gid.push_back(gr.first), off.push_back(tot), len.push_back((uint32_t)f.n);
+            if (f.n)
+                wj.push_back({j.dec_off, tot, f.n, 0, f.count, 0});
+            tot += (f.n + 15) & ~(uint64_t)15;
+        }
+        CHK(ensure(c, c->rd.d_pu_out, tot + 64));
+        CHK(unpack_write(c, wj, c->rd.d_pu_out.as<uint8_t>()));
+        CHK(agc_hip_ref_register_batch_dev(c, (uint32_t)gid.size(), gid.data(), c->rd.d_pu_out.as<uint8_t>(), off.data(), len.data(), nullptr, min_match_len));
+    }
+    // 6. agc_hip_sample_fasta's path, the deltas and raw symbols read where the parts stage left them
+    return write_sample(c, Y, c->rd.d_pu_dec.as<uint8_t>(), n_ctg, h_ctg_seg, h_names, h_name_off, line_length, h_text, d_text, T);
 }
 
 extern "C" {
@@ -304,6 +676,34 @@ int agc_hip_zstd_decode_batch_dev(agc_hip_ctx *c, uint32_t n, const uint8_t *h_s
                                   uint32_t *h_status)
 {
     return zstd_decode_impl(c, n, h_src, h_src_off, nullptr, d_out, out_cap, h_out_off, h_status);
+}
+
+int agc_hip_parts_unpack(agc_hip_ctx *c, uint32_t n, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap, uint8_t *h_out,
+                         uint64_t out_cap, uint64_t *h_out_off, uint32_t *h_count, uint32_t *h_seq_end, uint32_t *h_status)
+{
+    return parts_unpack_impl(c, n, h_parts, h_src, src_bytes, seq_cap, h_out, nullptr, out_cap, h_out_off, h_count, h_seq_end, h_status);
+}
+
+int agc_hip_parts_unpack_dev(agc_hip_ctx *c, uint32_t n, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap, uint8_t *d_out,
+                             uint64_t out_cap, uint64_t *h_out_off, uint32_t *h_count, uint32_t *h_seq_end, uint32_t *h_status)
+{
+    return parts_unpack_impl(c, n, h_parts, h_src, src_bytes, seq_cap, nullptr, d_out, out_cap, h_out_off, h_count, h_seq_end, h_status);
+}
+
+int agc_hip_sample_fasta_parts(agc_hip_ctx *c, uint32_t n_parts, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap, uint32_t n_ctg,
+                               const uint64_t *h_ctg_seg, const agc_hip_seg_part *h_seg, uint32_t k, uint32_t min_match_len, uint32_t line_length, const char *h_names,
+                               const uint64_t *h_name_off, uint8_t *h_text, uint64_t text_cap, uint64_t *h_text_len)
+{
+    return sample_fasta_parts_impl(c, n_parts, h_parts, h_src, src_bytes, seq_cap, n_ctg, h_ctg_seg, h_seg, k, min_match_len, line_length, h_names, h_name_off, h_text, nullptr,
+                                   text_cap, h_text_len);
+}
+
+int agc_hip_sample_fasta_parts_dev(agc_hip_ctx *c, uint32_t n_parts, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap, uint32_t n_ctg,
+                                   const uint64_t *h_ctg_seg, const agc_hip_seg_part *h_seg, uint32_t k, uint32_t min_match_len, uint32_t line_length, const char *h_names,
+                                   const uint64_t *h_name_off, uint8_t *d_text, uint64_t text_cap, uint64_t *h_text_len)
+{
+    return sample_fasta_parts_impl(c, n_parts, h_parts, h_src, src_bytes, seq_cap, n_ctg, h_ctg_seg, h_seg, k, min_match_len, line_length, h_names, h_name_off, nullptr, d_text,
+                                   text_cap, h_text_len);
 }
 
 } // extern "C"

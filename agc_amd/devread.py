@@ -1,11 +1,18 @@
-"""A sample's FASTA text written on the GPU: the host reader opens the archive and decodes the zstd parts (agc_amd/reader.py,
-libagc_read.so), everything behind that -- the LZ-diff decode, orientation, the k-symbol overlap, the alphabet and the line
-wrapping -- is one call of the device library (include/agc_hip.h: agc_hip_sample_fasta).
+"""A sample's FASTA text written on the GPU.  Two ways in, the same text out:
+
+sample_fasta / sample_fasta_dev: the host reader opens the archive and decodes the zstd parts (agc_amd/reader.py, libagc_read.so),
+everything behind that -- the LZ-diff decode, orientation, the k-symbol overlap, the alphabet and the line wrapping -- is one call
+of the device library (include/agc_hip.h: agc_hip_sample_fasta).
+
+sample_fasta_parts / sample_fasta_parts_dev: the host reader only reads the collection metadata and says which stored parts the
+sample needs (GetSampleParts); their bytes go to the device as the archive holds them and are zstd-decoded, cut into sequences,
+un-tupled and -- the references not registered yet -- registered there (agc_hip_sample_fasta_parts).
 
     ctx = capi.Context(0)
     r = DeviceReader(ctx, "collection.agc")
     text = r.sample_fasta("HG00438.1")          # bytes, what `agc getset` writes
     d = r.sample_fasta_dev("HG00438.1")         # the same as a torch uint8 tensor on the device
+    text = r.sample_fasta_parts("HG00438.1")    # the same bytes, nothing but metadata decoded on the host
     r.close()
 
 Group references are registered with the context once, as gid_base + group id: two readers on one context need disjoint ranges.
@@ -25,7 +32,7 @@ class DeviceReader:
         if not self.file.Open(path):
             raise RuntimeError(f"{path}: not a readable .agc archive")
         prm = self.file.GetParams()
-        self.k, self.min_match_len = prm["k"], prm["min_match_len"]
+        self.k, self.min_match_len, self.pack_cardinality = prm["k"], prm["min_match_len"], prm["pack_cardinality"]
         self.registered = set()
         self._pinned, self._pinned_cap = None, 0
 
@@ -80,4 +87,53 @@ class DeviceReader:
         if need:
             torch.cuda.synchronize()
             self.ctx.sample_fasta_dev(ctg_seg, segs, data, self.k, line_length, names, name_off, out.data_ptr(), need)
+        return out
+
+    def parts(self, name):
+        """the sample's stored parts (reader.CAGCFile.GetSampleParts, without the references registered already) -> (the arguments of
+        Context.sample_fasta_parts_raw in front of the text buffer, the groups whose references are among the parts)"""
+        if self.file is None:
+            raise RuntimeError("the reader is closed")
+        p = self.file.GetSampleParts(name, self.registered)
+        if p is None:
+            raise KeyError(name)
+        is_ref = p["part_content"] != reader.PART_PACK
+        parts = np.zeros(p["part_off"].size, capi.PART_DTYPE)
+        parts["off"], parts["n_bytes"], parts["coding"], parts["content"] = p["part_off"], p["part_bytes"], p["part_coding"], p["part_content"]
+        parts["gid"] = np.where(is_ref, p["part_group"] + np.uint32(self.gid_base), 0)  # (reader.PART_* and capi.PART_* are the same numbers)
+        segs = np.zeros(p["kind"].size, capi.SEG_PART_DTYPE)
+        segs["kind"] = p["kind"]
+        segs["gid"] = np.where(p["kind"] == capi.SEG_RAW, 0, p["group_id"] + np.uint32(self.gid_base))
+        segs["part"], segs["index"], segs["length"], segs["rc"] = p["seg_part"], p["seg_index"], p["length"], p["rc"]
+        args = (parts, (p["src"], p["src_bytes"]), self.pack_cardinality, p["ctg_seg"], segs, self.k, self.min_match_len)
+        return args, (p["names"], p["name_off"]), p["part_group"][is_ref].tolist()
+
+    def _after(self, rc, new_groups):
+        """a call that got as far as the registration has registered every new group, whatever it returned then; one refused before
+        that has registered none.  Which it was is asked of the context: a group registers once, so the set must be right."""
+        if new_groups and self.ctx.ref_registered(self.gid_base + new_groups[0]):
+            self.registered.update(new_groups)
+        self.ctx._chk(rc)
+
+    def sample_fasta_parts(self, name, line_length=80):
+        """-> bytes: sample_fasta's text; the host decodes nothing but the collection metadata, a refused part raises (no host fallback)"""
+        args, (names, name_off), new = self.parts(name)
+        rc, need = self.ctx.sample_fasta_parts_raw(*args, line_length, names, name_off, self._pinned, self._pinned_cap)
+        if rc == capi.ECAP:  # (the text's size follows from the segments' lengths: nothing was launched or registered)
+            rc, need = self.ctx.sample_fasta_parts_raw(*args, line_length, names, name_off, self._pinned_buffer(need), self._pinned_cap)
+        self._after(rc, new)
+        return C.string_at(self._pinned, need) if need else b""
+
+    def sample_fasta_parts_dev(self, name, line_length=80):
+        """-> the same text as a torch uint8 tensor on the context's device"""
+        import torch
+        args, (names, name_off), new = self.parts(name)
+        rc, need = self.ctx.sample_fasta_parts_raw(*args, line_length, names, name_off, None, 0, dev=True)
+        if rc != capi.ECAP:
+            self._after(rc, new)
+        out = torch.empty(need, dtype=torch.uint8, device="cuda")
+        if need:
+            torch.cuda.synchronize()
+            rc, _n = self.ctx.sample_fasta_parts_raw(*args, line_length, names, name_off, out.data_ptr(), need, dev=True)
+            self._after(rc, new)
         return out

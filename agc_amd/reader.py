@@ -11,8 +11,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libagc_read.so")
 SYMBOLS = ["agc_open", "agc_close", "agc_get_ctg_len", "agc_get_ctg_seq", "agc_n_sample", "agc_n_ctg", "agc_reference_sample",
            "agc_list_sample", "agc_list_ctg", "agc_list_destroy", "agc_string_destroy", "agc_get_sample_fasta", "agc_get_params",
-           "agc_get_sample_plan", "agc_plan_fields", "agc_plan_destroy"]
+           "agc_get_sample_plan", "agc_plan_fields", "agc_plan_destroy", "agc_get_sample_parts", "agc_parts_fields", "agc_parts_destroy"]
 PLAN_RAW, PLAN_REF, PLAN_DELTA = 0, 1, 2
+PART_STORED, PART_ZSTD = 0, 1
+PART_PACK, PART_REF_BYTES, PART_REF_TUPLES = 0, 1, 2
 
 
 class PlanView(C.Structure):
@@ -22,6 +24,16 @@ class PlanView(C.Structure):
                 ("names", C.c_void_p), ("name_off", _u64p), ("ctg_seg", _u64p),
                 ("group_id", _u32p), ("in_group_id", _u32p), ("rc", _u32p), ("length", _u32p), ("kind", _u32p), ("seg_bytes", _u32p),
                 ("off", _u64p), ("bytes", C.c_void_p), ("groups", _u32p), ("ref_off", _u64p), ("ref_bytes", C.c_void_p)]
+
+
+class PartsView(C.Structure):
+    """agc_parts_view (include/agc_read.h)"""
+    _u32p, _u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+    _fields_ = [("n_ctg", C.c_uint64), ("n_seg", C.c_uint64), ("n_parts", C.c_uint64), ("src_bytes", C.c_uint64), ("src", C.c_void_p),
+                ("names", C.c_void_p), ("name_off", _u64p), ("ctg_seg", _u64p),
+                ("group_id", _u32p), ("in_group_id", _u32p), ("rc", _u32p), ("length", _u32p), ("kind", _u32p), ("seg_part", _u32p), ("seg_index", _u32p),
+                ("part_off", _u64p), ("part_bytes", _u32p), ("part_coding", _u32p), ("part_content", _u32p), ("part_group", _u32p), ("part_no", _u32p)]
+
 
 _lib = None
 
@@ -56,6 +68,10 @@ def load():
     L.agc_get_sample_plan.argtypes = [vp, cp]
     L.agc_plan_fields.argtypes = [vp, C.POINTER(PlanView)]
     L.agc_plan_destroy.argtypes = [vp]
+    L.agc_get_sample_parts.restype = vp
+    L.agc_get_sample_parts.argtypes = [vp, cp, C.POINTER(C.c_uint32), C.c_uint64]
+    L.agc_parts_fields.argtypes = [vp, C.POINTER(PartsView)]
+    L.agc_parts_destroy.argtypes = [vp]
     _lib = L
     return L
 
@@ -192,3 +208,39 @@ class CAGCFile:
             return out
         finally:
             self.L.agc_plan_destroy(h)
+
+    def GetSampleParts(self, sample, have=()):
+        """the stored parts of a whole sample (agc_get_sample_parts) as numpy arrays of their own, or None for an unknown sample: names /
+        name_off, ctg_seg, per segment group_id / in_group_id / rc / length / kind (PLAN_*) / seg_part / seg_index, per part part_off /
+        part_bytes / part_coding (PART_STORED, PART_ZSTD) / part_content (PART_PACK, PART_REF_*) / part_group / part_no.  have: the
+        groups whose references the caller has already.  src / src_bytes: the address and size of the archive's bytes the parts lie
+        in -- the archive's own, valid until Close; part(i) copies one part out"""
+        import numpy as np
+        hv = np.ascontiguousarray(sorted(int(g) for g in have), dtype=np.uint32)
+        h = self.L.agc_get_sample_parts(self.h, sample.encode(), hv.ctypes.data_as(C.POINTER(C.c_uint32)), hv.size) if self.h else None
+        if not h:
+            return None
+        try:
+            v = PartsView()
+            if self.L.agc_parts_fields(h, C.byref(v)) != 0:
+                return None
+
+            def arr(ptr, n, dt):
+                n = int(n)
+                if not n:
+                    return np.zeros(0, dt)
+                addr = ptr if isinstance(ptr, int) else C.addressof(ptr.contents)
+                return np.frombuffer((C.c_char * (n * np.dtype(dt).itemsize)).from_address(addr), dtype=dt).copy()
+
+            out = {"name_off": arr(v.name_off, v.n_ctg + 1, np.uint64), "ctg_seg": arr(v.ctg_seg, v.n_ctg + 1, np.uint64)}
+            out["names"] = arr(v.names, out["name_off"][-1], np.uint8).tobytes()
+            for f in ("group_id", "in_group_id", "rc", "length", "kind", "seg_part", "seg_index"):
+                out[f] = arr(getattr(v, f), v.n_seg, np.uint32)
+            out["part_off"] = arr(v.part_off, v.n_parts, np.uint64)
+            for f in ("part_bytes", "part_coding", "part_content", "part_group", "part_no"):
+                out[f] = arr(getattr(v, f), v.n_parts, np.uint32)
+            out["src"], out["src_bytes"] = v.src, int(v.src_bytes)
+            out["part"] = lambda i: C.string_at(out["src"] + int(out["part_off"][i]), int(out["part_bytes"][i]))
+            return out
+        finally:
+            self.L.agc_parts_destroy(h)

@@ -64,7 +64,8 @@ enum {
     AGC_HIP_K_DECODE_WRITE = 13, /* lz_decode_write_kernel: the decoded symbols */
     AGC_HIP_K_FASTA_OUT = 14,    /* agc_hip_sample_fasta*: segment_copy_kernel + fasta_text_kernel (fasta_out_kernels.hip) */
     AGC_HIP_K_ZSTD_DECODE = 15,  /* agc_hip_zstd_decode_batch*: zstd_decode_kernel (zstd_decode_kernels.hip) */
-    AGC_HIP_K_COUNT = 16
+    AGC_HIP_K_PARTS_UNPACK = 16, /* agc_hip_parts_unpack*, agc_hip_sample_fasta_parts*: pack_index_kernel, tuples_size_kernel, tuples_unpack_kernel (parts_unpack_kernels.hip) */
+    AGC_HIP_K_COUNT = 17
 };
 int agc_hip_timing_enable(agc_hip_ctx *ctx, int on);
 int agc_hip_timing_reset(agc_hip_ctx *ctx);
@@ -516,6 +517,84 @@ int agc_hip_zstd_decode_batch(agc_hip_ctx *ctx, uint32_t n, const uint8_t *h_src
 /* the same, the decoded bytes left in device memory (d_out: out_cap bytes the caller owns) */
 int agc_hip_zstd_decode_batch_dev(agc_hip_ctx *ctx, uint32_t n, const uint8_t *h_src, const uint64_t *h_src_off, uint8_t *d_out, uint64_t out_cap,
                                   uint64_t *h_out_off, uint32_t *h_status);
+
+/* ---- the read side from the archive's parts: nothing but the collection metadata is decoded on the host --------------------------- */
+/* One stored part of an archive stream (src/common/archive.cpp:378-402) as the caller found it: its bytes are
+ * h_src[off, off + n_bytes) -- WITHOUT the marker byte the archive appends to a zstd part (src/common/segment.h:177-183) -- coded
+ * STORED (archive metadata 0: the bytes as they are) or ZSTD (one frame, what agc_hip_zstd_decode_batch takes).  What it holds:
+ * PACK, sequences each followed by one 0xFF (a delta or raw stream's pack, segment.cpp:150-165, 536-545); REF_BYTES, a group's
+ * reference, one symbol code per byte; REF_TUPLES, the same packed 2-4 symbols per byte with a marker byte at its end
+ * (tuples2bytes, segment.h:92-138).  gid: the group a reference is to be registered under (agc_hip_sample_fasta_parts). */
+enum { AGC_HIP_PART_STORED = 0, AGC_HIP_PART_ZSTD = 1 };
+enum { AGC_HIP_PART_PACK = 0, AGC_HIP_PART_REF_BYTES = 1, AGC_HIP_PART_REF_TUPLES = 2 };
+typedef struct {
+    uint64_t off;
+    uint32_t n_bytes;
+    uint32_t coding;  /* AGC_HIP_PART_STORED / _ZSTD */
+    uint32_t content; /* AGC_HIP_PART_PACK / _REF_BYTES / _REF_TUPLES */
+    uint32_t gid;
+} agc_hip_part;
+/* status of a part: the two refusals of the zstd decode keep their numbers (AGC_HIP_ZD_*); AGC_HIP_PART_BAD_TUPLES: a tuple
+ * stream shorter than 2 bytes, or whose marker says 2, 3 or 4 symbols per byte and more than that in its last byte (the host
+ * routine does not look and would read and write outside its buffers) */
+enum { AGC_HIP_PART_OK = 0, AGC_HIP_PART_BAD_TUPLES = 3 };
+
+/* A batch of parts into their final bytes on the device: the ZSTD parts through the zstd decode stage, the STORED ones uploaded beside
+ * them; then every PACK is cut at its terminators and every REF_TUPLES is unpacked.  Per part i: h_status[i]; its final bytes
+ * out[h_out_off[i], h_out_off[i+1]) -- a pack's decoded bytes, a reference's symbols; a refused part has none; a pack's
+ * h_count[i] = its sequences, exactly, and the first min(h_count[i], seq_cap) of their end offsets (= the offsets of their
+ * terminators: sequence q is the pack's bytes [end[q-1] + 1, end[q]), sequence 0 from 0; bytes behind the last terminator belong
+ * to none) in h_seq_end[i * seq_cap ...]; the rest of the row, and the rows and counts of the other parts, stay as they were.
+ * Everything is decoded into buffers of the context first, the sizes are known before anything is written to out:
+ * AGC_HIP_ECAP: out_cap is smaller than h_out_off[n]; offsets, counts, end offsets and statuses are filled, nothing is written to
+ * out.  AGC_HIP_EINVAL with the results filled: at least one part has a status != 0 (the error text names the first); it refuses
+ * nothing else of the batch -- the other parts are complete and correct, no byte outside their ranges is written.  AGC_HIP_EINVAL
+ * with nothing filled or launched: a part outside h_src (src_bytes), an unknown coding or content, a NULL that is needed.  n == 0:
+ * OK.  Runs on the context's first stream. */
+int agc_hip_parts_unpack(agc_hip_ctx *ctx, uint32_t n, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap,
+                         uint8_t *h_out, uint64_t out_cap, uint64_t *h_out_off, uint32_t *h_count, uint32_t *h_seq_end, uint32_t *h_status);
+/* the same, the final bytes left in device memory (d_out: out_cap bytes the caller owns, any alignment) */
+int agc_hip_parts_unpack_dev(agc_hip_ctx *ctx, uint32_t n, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap,
+                             uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_off, uint32_t *h_count, uint32_t *h_seq_end, uint32_t *h_status);
+
+/* One segment of a contig, its bytes named by where they lie in the archive: RAW and DELTA are sequence `index` of the pack
+ * h_parts[part]; REF and DELTA name their group, which is registered or has its reference among the parts.  length: the symbols the
+ * segment has, overlap included (the collection's raw_length). */
+typedef struct {
+    uint32_t kind;   /* AGC_HIP_SEG_* */
+    uint32_t gid;    /* REF, DELTA */
+    uint32_t part;   /* RAW, DELTA */
+    uint32_t index;
+    uint32_t length;
+    uint32_t rc;
+} agc_hip_seg_part;
+
+/* agc_hip_sample_fasta for a sample whose packs and new references are still archive parts: the contigs, names, k, line_length and
+ * text of that call; h_parts / h_src / seq_cap as agc_hip_parts_unpack takes them (seq_cap >= every index + 1: the archive's pack
+ * cardinality); every REF_* part is a NEW reference, registered under its gid with min_match_len.  In this order:
+ *  1. *h_text_len = the text's size, from the segments' lengths alone.  AGC_HIP_ECAP: text_cap is smaller; nothing was launched.
+ *  2. Refused before any launch: a reference part whose group is registered already or named twice (AGC_HIP_EINVAL), a REF / DELTA
+ *     whose group is neither registered nor among the parts (AGC_HIP_ENOREF), a RAW / DELTA whose part is not a PACK of the batch,
+ *     an unknown kind, a part outside h_src, a min_match_len agc_hip_ref_register refuses (AGC_HIP_EINVAL).
+ *  3. The parts are unpacked on the device; counts, end offsets, reference sizes and statuses come back in one copy.
+ *  4. AGC_HIP_EINVAL, the error text naming the part or segment: a refused part; an index at or above its pack's count (or above
+ *     seq_cap); a RAW whose sequence, or a REF whose reference, has another size than `length`; a segment behind a contig's first
+ *     shorter than k.  NO reference has been registered, nothing has been written to the text: the context is as it was.
+ *  5. The new references are registered in one batch, from the device buffer.
+ *  6. agc_hip_sample_fasta's path -- the deltas scanned against their lengths, then written; the copies; the text -- reading
+ *     the deltas and raw symbols where step 3 left them.  A refusal here (a malformed delta, a delta of another length:
+ *     AGC_HIP_EINVAL, nothing written to the text) does NOT undo step 5: the new references stay registered and valid, and a
+ *     caller must not hand their parts in again.
+ * No pack byte and no reference symbol goes back to the host.  Runs on the context's first stream. */
+int agc_hip_sample_fasta_parts(agc_hip_ctx *ctx, uint32_t n_parts, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap,
+                               uint32_t n_ctg, const uint64_t *h_ctg_seg, const agc_hip_seg_part *h_seg, uint32_t k, uint32_t min_match_len,
+                               uint32_t line_length, const char *h_names, const uint64_t *h_name_off, uint8_t *h_text, uint64_t text_cap,
+                               uint64_t *h_text_len);
+/* the same, the text left in device memory (d_text: text_cap bytes the caller owns, any alignment) */
+int agc_hip_sample_fasta_parts_dev(agc_hip_ctx *ctx, uint32_t n_parts, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap,
+                                   uint32_t n_ctg, const uint64_t *h_ctg_seg, const agc_hip_seg_part *h_seg, uint32_t k, uint32_t min_match_len,
+                                   uint32_t line_length, const char *h_names, const uint64_t *h_name_off, uint8_t *d_text, uint64_t text_cap,
+                                   uint64_t *h_text_len);
 
 #ifdef __cplusplus
 }

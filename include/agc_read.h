@@ -6,7 +6,8 @@
  * (zstd + LZ-diff decode + reverse complement + stitching) is not part of the GPU hot path.
  * Two additions, marked "extension", return FASTA text the way `agc getset` / `agc getctg` write it; a third hands out the
  * PLAN of a sample -- what is left to do behind zstd -- for a caller that assembles the text elsewhere (agc_amd/devread.py: on
- * the GPU, include/agc_hip.h: agc_hip_sample_fasta).  This library itself stays host code.
+ * the GPU, include/agc_hip.h: agc_hip_sample_fasta); a fourth hands out the stored PARTS the sample touches, undecoded, for a caller
+ * that also decodes elsewhere (agc_hip_sample_fasta_parts).  This library itself stays host code.
  */
 #ifndef AGC_READ_H
 #define AGC_READ_H
@@ -73,6 +74,37 @@ agc_plan_t *agc_get_sample_plan(const agc_t *agc, const char *sample);
 int agc_plan_fields(const agc_plan_t *plan, agc_plan_view *out);
 /* frees the plan (NULL: nothing to do); returns 0 */
 int agc_plan_destroy(agc_plan_t *plan);
+
+/* extension: the stored PARTS of a whole sample -- the plan above without its decode, for a caller that decodes elsewhere
+ * (agc_amd/devread.py: on the GPU, include/agc_hip.h: agc_hip_sample_fasta_parts).  Contigs, names and the segments' group,
+ * index in the group, orientation and kind as in the plan; length is the length the collection stores for the segment; a RAW or
+ * DELTA segment is sequence seg_index (counted from 0) of the pack seg_part.  The n_parts distinct parts the sample touches:
+ * part 0 of the reference stream of every group >= 16 that is not among have_groups (ascending by group), then pack
+ * index / pack_cardinality of the delta stream of every group a RAW or DELTA segment names.  Part i is the bytes
+ * src[part_off[i], part_off[i] + part_bytes[i]) of the archive, coded AGC_PART_STORED (as they are) or AGC_PART_ZSTD (one frame; the
+ * marker byte the archive keeps behind it is not counted), and holds AGC_PART_PACK (sequences, each followed by 0xFF),
+ * AGC_PART_REF_BYTES (a reference, one symbol per byte) or AGC_PART_REF_TUPLES (a reference packed 2-4 symbols per byte, its marker
+ * byte last); part_group / part_no: its group and, for a pack, its number in the stream.  Nothing is decompressed and none of the
+ * reader's caches is touched.  src belongs to the archive (valid until agc_close), everything else to the parts object. */
+enum { AGC_PART_STORED = 0, AGC_PART_ZSTD = 1 };
+enum { AGC_PART_PACK = 0, AGC_PART_REF_BYTES = 1, AGC_PART_REF_TUPLES = 2 };
+typedef struct agc_parts_t agc_parts_t;
+typedef struct {
+    uint64_t n_ctg, n_seg, n_parts, src_bytes;
+    const uint8_t *src;
+    const char *names;
+    const uint64_t *name_off; /* n_ctg + 1 */
+    const uint64_t *ctg_seg;  /* n_ctg + 1 */
+    const uint32_t *group_id, *in_group_id, *rc, *length, *kind, *seg_part, *seg_index; /* n_seg each */
+    const uint64_t *part_off;                                                           /* n_parts */
+    const uint32_t *part_bytes, *part_coding, *part_content, *part_group, *part_no;     /* n_parts each */
+} agc_parts_view;
+/* NULL for an unknown sample or a part the archive does not hold */
+agc_parts_t *agc_get_sample_parts(const agc_t *agc, const char *sample, const uint32_t *have_groups, uint64_t n_have);
+/* fills *out; 0 for success */
+int agc_parts_fields(const agc_parts_t *parts, agc_parts_view *out);
+/* frees the parts object (NULL: nothing to do); returns 0 */
+int agc_parts_destroy(agc_parts_t *parts);
 
 #ifdef __cplusplus
 }
