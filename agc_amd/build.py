@@ -26,7 +26,7 @@ class _Locked:
         fcntl.flock(self.f, fcntl.LOCK_UN)
         self.f.close()
 LIB = os.path.join(HERE, "libagc_hip.so")
-SOURCES = ["api.hip", "read_api.hip", "fasta_plan.h", "lz_plan.h", "lz_consts.h", "scan_kernels.hip", "pack_kernels.hip", "lz_kernels.hip", "splitters.hip", "zstd_kernels.hip", "seg_kernels.hip", "segments.hip", "lz_decode_kernels.hip", "lz_decode.h", "fasta_out_kernels.hip", "fasta_out.h",
+SOURCES = ["api.hip", "read_api.hip", "range_kernels.hip", "range_clip.h", "range_plan.h", "fasta_plan.h", "lz_plan.h", "lz_consts.h", "scan_kernels.hip", "pack_kernels.hip", "lz_kernels.hip", "splitters.hip", "zstd_kernels.hip", "seg_kernels.hip", "segments.hip", "lz_decode_kernels.hip", "lz_decode.h", "fasta_out_kernels.hip", "fasta_out.h",
            "zstd_decode_kernels.hip", "zstd/zs_decode.h", "parts_unpack_kernels.hip", "parts_unpack.h", "dev_common.h", "sym_view.h",
            "zstd/zs_common.h", "zstd/zs_opt.h", "zstd/zs_opt_sm.h", "zstd/zs_opt_grp.h", "zstd/zs_entropy.h", "zstd/zs_frame.h", "zstd/zs_params.h"]
 
@@ -58,7 +58,7 @@ HOST = os.path.join(CSRC, "host")
 HOST_LIB = os.path.join(HERE, "libagc_host.so")
 HOST_BIN = os.path.join(HERE, "bin", "agc_amd")
 HOST_SOURCES = ["compressor.cpp", "compressor_batch.cpp", "compressor_dist.cpp", "compressor_impl.h", "compressor.h", "host_support.h", "switches.h",
-                "capi_host.cpp", "main.cpp", "reader.cpp", "reader.h", "capi_read.cpp", "archive_read.h"]
+                "capi_host.cpp", "main.cpp", "reader.cpp", "reader.h", "capi_read.cpp", "archive_read.h", "../range_plan.h"]
 HOST_LIB_SOURCES = ["compressor.cpp", "compressor_batch.cpp", "compressor_dist.cpp", "capi_host.cpp", "reader.cpp"]
 READ_LIB = os.path.join(HERE, "libagc_read.so")
 
@@ -66,7 +66,7 @@ READ_LIB = os.path.join(HERE, "libagc_read.so")
 def build_read(force=False, verbose=False):
     """g++ for the read side (include/agc_read.h): libagc_read.so -- host only, no HIP dependency."""
     srcs = [os.path.join(HOST, s) for s in ("reader.cpp", "capi_read.cpp")]
-    deps = srcs + [os.path.join(HOST, "reader.h"), os.path.join(HOST, "archive_read.h"), os.path.join(HERE, "..", "include", "agc_read.h")]
+    deps = srcs + [os.path.join(HOST, "reader.h"), os.path.join(HOST, "archive_read.h"), os.path.join(CSRC, "range_plan.h"), os.path.join(HERE, "..", "include", "agc_read.h")]
     with _Locked():
         if not force and os.path.exists(READ_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(READ_LIB) for d in deps):
             return READ_LIB

@@ -16,7 +16,7 @@ OK, ENODEV, EINVAL, ENOMEM, ECAP, ENOREF = 0, -1, -2, -3, -4, -5
 K_SCAN, K_INDEX, K_ENCODE, K_ESTIMATE, K_COSTVEC, K_REVCOMP, K_PREPROCESS, K_REFSTORE = range(8)
 K_NAMES = ["scan", "index", "encode", "estimate", "costvec", "revcomp", "preprocess", "refstore", "zstd", "filter", "segments", "pack",
            "decode_scan", "decode_write", "fasta_out"]
-K_NAMES_MORE = ["zstd_decode", "parts_unpack"]  # the slots from 15 on (K_NAMES stays the 15 slots its users count on); timing_get reports both
+K_NAMES_MORE = ["zstd_decode", "parts_unpack", "ranges"]  # the slots from 15 on (K_NAMES stays the 15 slots its users count on); timing_get reports both
 ZD_OK, ZD_UNSUPPORTED, ZD_MALFORMED = 0, 1, 2
 SEG_RAW, SEG_REF, SEG_DELTA = 0, 1, 2
 PART_STORED, PART_ZSTD = 0, 1
@@ -35,9 +35,10 @@ SYMBOLS = [
     "agc_hip_ref_register", "agc_hip_ref_register_batch_dev", "agc_hip_ref_get", "agc_hip_ref_index_get",
     "agc_hip_lz_encode_batch_dev", "agc_hip_lz_encode_batch", "agc_hip_lz_encode_begin_dev", "agc_hip_lz_encode_end", "agc_hip_lz_encode_pending",
     "agc_hip_lz_encode_begin_packed_on", "agc_hip_lz_encode_end_on", "agc_hip_lz_encode_pending_on", "agc_hip_lz_encode_drop_on",
-    "agc_hip_lz_decode_batch", "agc_hip_lz_decode_batch_dev",
+    "agc_hip_lz_decode_batch", "agc_hip_lz_decode_batch_dev", "agc_hip_lz_decode_window_batch", "agc_hip_lz_decode_window_batch_dev",
     "agc_hip_sample_fasta", "agc_hip_sample_fasta_dev",
     "agc_hip_parts_unpack", "agc_hip_parts_unpack_dev", "agc_hip_sample_fasta_parts", "agc_hip_sample_fasta_parts_dev",
+    "agc_hip_ranges_parts", "agc_hip_ranges_parts_dev",
     "agc_hip_host_alloc", "agc_hip_host_free",
     "agc_hip_lz_estimate_batch_dev", "agc_hip_lz_estimate_batch",
     "agc_hip_lz_cost_vector_batch_dev", "agc_hip_lz_cost_vector_batch",
@@ -85,6 +86,8 @@ class SegSrc(C.Structure):
 SEG_SRC_DTYPE = np.dtype([("kind", "<u4"), ("gid", "<u4"), ("off", "<u8"), ("n_bytes", "<u4"), ("length", "<u4"), ("rc", "<u4"), ("pad", "<u4")])
 PART_DTYPE = np.dtype([("off", "<u8"), ("n_bytes", "<u4"), ("coding", "<u4"), ("content", "<u4"), ("gid", "<u4")])  # agc_hip_part
 SEG_PART_DTYPE = np.dtype([("kind", "<u4"), ("gid", "<u4"), ("part", "<u4"), ("index", "<u4"), ("length", "<u4"), ("rc", "<u4")])  # agc_hip_seg_part
+SEG_WIN_DTYPE = np.dtype([("kind", "<u4"), ("gid", "<u4"), ("part", "<u4"), ("index", "<u4"), ("length", "<u4"), ("rc", "<u4"), ("win_from", "<u4"),
+                          ("win_len", "<u4")])  # agc_hip_seg_win
 SEGMENT_DTYPE = np.dtype([("start", "<u8"), ("front_dir", "<u8"), ("front_rc", "<u8"), ("back_dir", "<u8"), ("back_rc", "<u8"), ("ctg", "<u4"), ("len", "<u4"),
                           ("map_gid", "<i4"), ("front_full", "u1"), ("back_full", "u1"), ("store_rc", "u1"), ("encoded", "u1")])
 GROUP_SLOT_DTYPE = np.dtype([("k1", "<u8"), ("k2", "<u8"), ("gid", "<i4"), ("used", "<u4")])
@@ -147,6 +150,8 @@ def load():
     L.agc_hip_lz_encode_pending.argtypes = [vp, u32p]
     L.agc_hip_lz_decode_batch.argtypes = [vp, C.c_uint32, u32p, u8p, u64p, u8p, u8p, C.c_uint64, u64p]
     L.agc_hip_lz_decode_batch_dev.argtypes = [vp, C.c_uint32, u32p, u8p, u64p, u8p, vp, C.c_uint64, u64p]
+    L.agc_hip_lz_decode_window_batch.argtypes = [vp, C.c_uint32, u32p, u8p, u64p, u8p, u32p, u32p, vp, C.c_uint64, u64p]
+    L.agc_hip_lz_decode_window_batch_dev.argtypes = [vp, C.c_uint32, u32p, u8p, u64p, u8p, u32p, u32p, vp, C.c_uint64, u64p]
     fasta_head = [vp, C.c_uint32, u64p, C.POINTER(SegSrc), u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_char_p, u64p]
     L.agc_hip_sample_fasta.argtypes = fasta_head + [vp, C.c_uint64, u64p]
     L.agc_hip_sample_fasta_dev.argtypes = fasta_head + [vp, C.c_uint64, u64p]
@@ -156,6 +161,9 @@ def load():
     fasta_parts = parts_head + [C.c_uint32, u64p, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, u64p, vp, C.c_uint64, u64p]
     L.agc_hip_sample_fasta_parts.argtypes = fasta_parts
     L.agc_hip_sample_fasta_parts_dev.argtypes = fasta_parts
+    ranges_parts = parts_head + [C.c_uint32, u64p, vp, C.c_uint32, C.c_int, vp, C.c_uint64, u64p]
+    L.agc_hip_ranges_parts.argtypes = ranges_parts
+    L.agc_hip_ranges_parts_dev.argtypes = ranges_parts
     L.agc_hip_host_alloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
     L.agc_hip_host_free.argtypes = [vp, vp]
     L.agc_hip_lz_estimate_batch_dev.argtypes = [vp, C.c_uint32, u32p, vp, u64p, u32p, u8p, u32p, u32p]
@@ -671,6 +679,29 @@ class Context:
         self._chk(self.L.agc_hip_lz_decode_batch_dev(self.h, g.size, _p(g, u32p), _p(e, u8p), _p(eo, u64p), _p(r, u8p), d_out, out_cap, _p(ooff, u64p)))
         return ooff
 
+    def lz_decode_window_batch_raw(self, enc, enc_off, gids, win_from, win_len, out_ptr, out_cap, rc=None, dev=False):
+        """the entry point itself (agc_hip_lz_decode_window_batch, dev: _dev) -> (return code, out_off[n+1])"""
+        e, eo, g, r = self._decode_args(enc, enc_off, gids, rc)
+        wf, wl = _a(win_from, np.uint32), _a(win_len, np.uint32)
+        assert wf.size == g.size and wl.size == g.size
+        ooff = np.zeros(g.size + 1, np.uint64)
+        fn = self.L.agc_hip_lz_decode_window_batch_dev if dev else self.L.agc_hip_lz_decode_window_batch
+        rc_ = fn(self.h, g.size, _p(g, u32p), _p(e, u8p), _p(eo, u64p), _p(r, u8p), _p(wf, u32p), _p(wl, u32p), out_ptr, int(out_cap), _p(ooff, u64p))
+        return rc_, ooff
+
+    def lz_decode_window_batch(self, enc, enc_off, gids, win_from, win_len, rc=None):
+        """of the oriented symbols delta s decodes to, only [win_from[s], win_from[s] + win_len[s]) -> (symbols, out_off[n+1])"""
+        out = np.empty(int(_a(win_len, np.uint32).astype(np.uint64).sum()), np.uint8)
+        rc_, ooff = self.lz_decode_window_batch_raw(enc, enc_off, gids, win_from, win_len, out.ctypes.data, out.size, rc=rc)
+        self._chk(rc_)
+        return out, ooff
+
+    def lz_decode_window_batch_dev(self, enc, enc_off, gids, win_from, win_len, d_out, out_cap, rc=None):
+        """the same, the windows left at the device address d_out (out_cap bytes) -> out_off[n+1]"""
+        rc_, ooff = self.lz_decode_window_batch_raw(enc, enc_off, gids, win_from, win_len, d_out, out_cap, rc=rc, dev=True)
+        self._chk(rc_)
+        return ooff
+
     def _fasta_args(self, ctg_seg, segs, data, names, name_off):
         cs, no = _a(ctg_seg, np.uint64), _a(name_off, np.uint64)
         sg = np.ascontiguousarray(segs, dtype=SEG_SRC_DTYPE)
@@ -759,6 +790,19 @@ class Context:
         rc_, n = self.sample_fasta_parts_raw(parts, src, seq_cap, ctg_seg, segs, k, min_match_len, line_length, names, name_off, d_text, text_cap, dev=True)
         self._chk(rc_)
         return n
+
+    def ranges_parts_raw(self, parts, src, seq_cap, q_seg, wins, min_match_len, letters, out_ptr, out_cap, dev=False):
+        """the entry point itself (agc_hip_ranges_parts, dev: _dev) -> (return code, out_off[n_q+1]); wins: SEG_WIN_DTYPE, query q =
+        wins[q_seg[q]:q_seg[q+1]]"""
+        pt, sp, sn, _keep = self._parts_args(parts, src)
+        qs = _a(q_seg, np.uint64)
+        wn = np.ascontiguousarray(wins, dtype=SEG_WIN_DTYPE)
+        assert qs.size >= 1 and (qs.size == 1 or int(qs[-1]) == wn.size)
+        ooff = np.zeros(qs.size, np.uint64)
+        fn = self.L.agc_hip_ranges_parts_dev if dev else self.L.agc_hip_ranges_parts
+        rc_ = fn(self.h, pt.size, pt.ctypes.data, sp, sn, int(seq_cap), qs.size - 1, _p(qs, u64p), wn.ctypes.data, int(min_match_len), 1 if letters else 0,
+                 out_ptr, int(out_cap), _p(ooff, u64p))
+        return rc_, ooff
 
     def lz_encode_batch(self, text, gids, off, length, rc=None, enc_cap=None):
         text = _a(text, np.uint8)

@@ -19,6 +19,10 @@ struct agc_parts_t {
     agc::SampleParts p;
 };
 
+struct agc_ranges_t {
+    agc::RangeParts p;
+};
+
 static char **vec2list(const std::vector<std::string> &v)
 {
     char **list = (char **)malloc(sizeof(char *) * (v.size() + 1));
@@ -254,6 +258,63 @@ int agc_parts_fields(const agc_parts_t *parts, agc_parts_view *out)
 int agc_parts_destroy(agc_parts_t *parts)
 {
     delete parts;
+    return 0;
+}
+
+agc_ranges_t *agc_get_range_parts(const agc_t *agc, uint64_t n_q, const char *const *samples, const char *const *names, const int64_t *from, const int64_t *to,
+                                  const uint32_t *have_groups, uint64_t n_have, int64_t *bad_query)
+{
+    if (bad_query)
+        *bad_query = -1;
+    if (!agc || (n_q && (!names || !from || !to)) || (n_have && !have_groups))
+        return nullptr;
+    std::vector<agc::RangeQuery> q((size_t)n_q);
+    for (size_t i = 0; i < q.size(); ++i) {
+        if (!names[i])
+            return nullptr;
+        q[i] = {samples && samples[i] ? samples[i] : "", names[i], from[i], to[i]};
+    }
+    agc_ranges_t *r = new agc_ranges_t;
+    if (!agc->f.GetRangeParts(q, have_groups, (size_t)n_have, r->p, bad_query)) {
+        delete r;
+        return nullptr;
+    }
+    return r;
+}
+
+int agc_ranges_fields(const agc_ranges_t *ranges, agc_ranges_view *out)
+{
+    if (!ranges || !out)
+        return -1;
+    const agc::RangeParts &p = ranges->p;
+    out->n_q = p.q_len.size();
+    out->n_win = p.kind.size();
+    out->n_parts = p.part_off.size();
+    out->src_bytes = p.src_bytes;
+    out->src = p.src;
+    out->q_seg = p.q_seg.data();
+    out->q_len = p.q_len.data();
+    out->group_id = p.group_id.data();
+    out->in_group_id = p.in_group_id.data();
+    out->rc = p.rc.data();
+    out->length = p.length.data();
+    out->kind = p.kind.data();
+    out->seg_part = p.part.data();
+    out->seg_index = p.index.data();
+    out->win_from = p.win_from.data();
+    out->win_len = p.win_len.data();
+    out->part_off = p.part_off.data();
+    out->part_bytes = p.part_bytes.data();
+    out->part_coding = p.part_coding.data();
+    out->part_content = p.part_content.data();
+    out->part_group = p.part_group.data();
+    out->part_no = p.part_no.data();
+    return 0;
+}
+
+int agc_ranges_destroy(agc_ranges_t *ranges)
+{
+    delete ranges;
     return 0;
 }
 }

@@ -12,6 +12,7 @@
 #include <thread>
 #include <unordered_map>
 
+#include "../range_plan.h"
 #include "archive_read.h"
 
 namespace agc {
@@ -589,6 +590,43 @@ bool CAGCFile::GetSamplePlan(const std::string &sample, SamplePlan &P) const
     return true;
 }
 
+// The part lists of SampleParts / RangeParts (P: either), the segments in P already: the references of `refs` ascending by group,
+// then the packs of `packs` ((group, pack number) -> its place among the parts, filled here), and every RAW / DELTA segment's part.
+// false: a part the archive does not hold
+template <class P_t>
+static bool list_parts(const Archive &ar, uint32_t pack_cardinality, const std::map<uint32_t, uint32_t> &refs, std::map<std::pair<uint32_t, uint32_t>, uint32_t> &packs, P_t &P)
+{
+    auto add = [&](const std::string &stream, uint32_t no, uint32_t group, bool ref) {
+        const uint8_t *ptr;
+        uint64_t size, meta;
+        if (!ar.get_part(stream, no, ptr, size, meta) || size > 0xFFFFFFFFull || (meta != 0 && size < 1))
+            return false;
+        // (decode_ref_part / decode_pack_part: metadata 0 = stored as it is; otherwise a frame and one marker byte, which for a
+        // reference says whether the frame holds tuples)
+        P.part_off.push_back((uint64_t)(ptr - P.src));
+        P.part_bytes.push_back((uint32_t)(meta ? size - 1 : size));
+        P.part_coding.push_back(meta ? SampleParts::ZSTD : SampleParts::STORED);
+        P.part_content.push_back(!ref ? SampleParts::PACK : meta && ptr[size - 1] != 0 ? SampleParts::REF_TUPLES : SampleParts::REF_BYTES);
+        P.part_group.push_back(group);
+        P.part_no.push_back(no);
+        return true;
+    };
+    for (const auto &r : refs)
+        if (!add("x" + int_to_base64(r.first) + "r", 0, r.first, true))
+            return false;
+    for (auto &k : packs) {
+        k.second = (uint32_t)P.part_off.size();
+        if (!add("x" + int_to_base64(k.first.first) + "d", k.first.second, k.first.first, false))
+            return false;
+    }
+    for (size_t s = 0; s < P.kind.size(); ++s)
+        if (P.kind[s] != SamplePlan::REF) {
+            const uint32_t i = P.kind[s] == SamplePlan::RAW ? P.in_group_id[s] : P.in_group_id[s] - 1;
+            P.part[s] = packs[std::make_pair(P.group_id[s], i / pack_cardinality)];
+        }
+    return true;
+}
+
 // GetSamplePlan without its decode: which parts decode_ref_part / decode_pack_part would be handed, and how they would read them
 bool CAGCFile::GetSampleParts(const std::string &sample, const uint32_t *have_groups, size_t n_have, SampleParts &P) const
 {
@@ -631,35 +669,60 @@ bool CAGCFile::GetSampleParts(const std::string &sample, const uint32_t *have_gr
         }
         P.ctg_seg.push_back(P.kind.size());
     }
-    auto add = [&](const std::string &stream, uint32_t no, uint32_t group, bool ref) {
-        const uint8_t *ptr;
-        uint64_t size, meta;
-        if (!p->ar.get_part(stream, no, ptr, size, meta) || size > 0xFFFFFFFFull || (meta != 0 && size < 1))
+    return list_parts(p->ar, p->pack, refs, packs, P);
+}
+
+// The same for a batch of contig ranges: every query's contig is looked up as GetCtgSeq does, its windows are range_plan.h's, and the
+// parts are those of the segments that got a window -- each once for the whole batch
+bool CAGCFile::GetRangeParts(const std::vector<RangeQuery> &queries, const uint32_t *have_groups, size_t n_have, RangeParts &P, int64_t *bad_query) const
+{
+    if (bad_query)
+        *bad_query = -1;
+    if (!p->opened)
+        return false;
+    P = RangeParts();
+    P.src = p->ar.data.data();
+    P.src_bytes = p->ar.data.size();
+    std::vector<uint32_t> have(have_groups, have_groups + (have_groups ? n_have : 0));
+    std::sort(have.begin(), have.end());
+    std::map<uint32_t, uint32_t> refs;
+    std::map<std::pair<uint32_t, uint32_t>, uint32_t> packs;
+    P.q_seg.push_back(0);
+    for (size_t q = 0; q < queries.size(); ++q) {
+        uint32_t sid, cid;
+        if (p->find_contig(queries[q].sample, queries[q].name, sid, cid) < 0) {
+            if (bad_query)
+                *bad_query = (int64_t)q;
             return false;
-        // (decode_ref_part / decode_pack_part: metadata 0 = stored as it is; otherwise a frame and one marker byte, which for a
-        // reference says whether the frame holds tuples)
-        P.part_off.push_back((uint64_t)(ptr - P.src));
-        P.part_bytes.push_back((uint32_t)(meta ? size - 1 : size));
-        P.part_coding.push_back(meta ? SampleParts::ZSTD : SampleParts::STORED);
-        P.part_content.push_back(!ref ? SampleParts::PACK : meta && ptr[size - 1] != 0 ? SampleParts::REF_TUPLES : SampleParts::REF_BYTES);
-        P.part_group.push_back(group);
-        P.part_no.push_back(no);
-        return true;
-    };
-    for (const auto &r : refs)
-        if (!add("x" + int_to_base64(r.first) + "r", 0, r.first, true))
-            return false;
-    for (auto &k : packs) {
-        k.second = (uint32_t)P.part_off.size();
-        if (!add("x" + int_to_base64(k.first.first) + "d", k.first.second, k.first.first, false))
-            return false;
-    }
-    for (size_t s = 0; s < P.kind.size(); ++s)
-        if (P.kind[s] != SamplePlan::REF) {
-            const uint32_t i = P.kind[s] == SamplePlan::RAW ? P.in_group_id[s] : P.in_group_id[s] - 1;
-            P.part[s] = packs[std::make_pair(P.group_id[s], i / p->pack)];
         }
-    return true;
+        const std::vector<SegDesc> &segs = p->samples[sid].ctgs[cid].segs;
+        const uint64_t n = rp::contig_windows(
+            segs.size(), [&](uint64_t s) { return segs[s].raw_length; }, p->k, queries[q].from, queries[q].to, [&](uint64_t si, uint32_t win_from, uint32_t win_len) {
+                const SegDesc &s = segs[si];
+                const bool raw = s.group_id < NO_RAW_GROUPS;
+                const uint32_t kind = raw ? SamplePlan::RAW : s.in_group_id == 0 ? SamplePlan::REF : SamplePlan::DELTA;
+                uint32_t idx = 0;
+                if (kind != SamplePlan::REF) {
+                    const uint32_t i = raw ? s.in_group_id : s.in_group_id - 1;
+                    packs.emplace(std::make_pair(s.group_id, i / p->pack), 0);
+                    idx = i % p->pack;
+                }
+                if (!raw && !std::binary_search(have.begin(), have.end(), s.group_id))
+                    refs.emplace(s.group_id, 0);
+                P.group_id.push_back(s.group_id);
+                P.in_group_id.push_back(s.in_group_id);
+                P.rc.push_back(s.rc ? 1 : 0);
+                P.length.push_back(s.raw_length);
+                P.kind.push_back(kind);
+                P.part.push_back(0); // (filled by list_parts)
+                P.index.push_back(idx);
+                P.win_from.push_back(win_from);
+                P.win_len.push_back(win_len);
+            });
+        P.q_len.push_back(n);
+        P.q_seg.push_back(P.kind.size());
+    }
+    return list_parts(p->ar, p->pack, refs, packs, P);
 }
 
 bool CAGCFile::GetSampleFasta(const std::string &sample, std::string &out, uint32_t line_length) const

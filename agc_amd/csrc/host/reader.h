@@ -46,6 +46,29 @@ struct SampleParts {
     uint64_t src_bytes = 0;
 };
 
+// One query of a batch of contig ranges (GetRangeParts): contig `name` of `sample` (empty: the name must be unique in the archive),
+// positions [from, to] inclusive, read by GetCtgSeq's rules.
+struct RangeQuery {
+    std::string sample, name;
+    int64_t from, to;
+};
+
+// What a device needs to fetch a batch of contig ranges from the archive's own bytes (GetRangeParts): per query the windows of the
+// segments it touches, and the distinct stored parts of the whole batch as SampleParts lists them.
+struct RangeParts {
+    std::vector<uint64_t> q_seg; // n_q + 1: query q owns the window entries [q_seg[q], q_seg[q + 1])
+    std::vector<uint64_t> q_len; // n_q: the symbols query q yields (0: a range at or behind the contig's end)
+    // per window entry: the segment as SampleParts has it, and the window [win_from, win_from + win_len) of its ORIENTED symbols
+    // (win_len >= 1; behind a contig's first segment win_from >= k: the overlap is accounted for).  A query's windows back to back
+    // are its symbols
+    std::vector<uint32_t> group_id, in_group_id, rc, length, kind, part, index, win_from, win_len;
+    // per part, as in SampleParts: the new references ascending by group, then the packs
+    std::vector<uint64_t> part_off;
+    std::vector<uint32_t> part_bytes, part_coding, part_content, part_group, part_no;
+    const uint8_t *src = nullptr;
+    uint64_t src_bytes = 0;
+};
+
 class CAGCFile {
     struct Impl;
     std::unique_ptr<Impl> p;
@@ -81,6 +104,10 @@ public:
     // part 0 of x<group>r for every group >= 16 the sample touches that is not among have_groups; false: unknown sample, a part the
     // archive does not hold
     bool GetSampleParts(const std::string &sample, const uint32_t *have_groups, size_t n_have, SampleParts &parts) const;
+    // the windows and stored parts of a batch of contig ranges (see RangeParts; the arithmetic: ../range_plan.h); nothing is
+    // decompressed, no cache is touched.  false: an unknown or ambiguous contig -- *bad_query (when given) is the first such query --
+    // or a part the archive does not hold (*bad_query = -1)
+    bool GetRangeParts(const std::vector<RangeQuery> &queries, const uint32_t *have_groups, size_t n_have, RangeParts &parts, int64_t *bad_query = nullptr) const;
     // one `agc getctg` query -- contig[@sample][:from-to] (agc_decompressor_lib.h:127-130) -- as FASTA text;
     // the header is the full contig name (+ ":from-to" when a range was given), core/agc_decompressor.cpp:478-567
     bool GetContigFasta(const std::string &query, std::string &out, uint32_t line_length, std::string &err) const;

@@ -1,12 +1,14 @@
 // read_api.hip -- the read path of include/agc_hip.h on the context's first stream: agc_hip_zstd_decode_batch (frames -> bytes),
 // agc_hip_lz_decode_batch (deltas -> symbols), agc_hip_sample_fasta (a sample's plan -> its FASTA text), agc_hip_parts_unpack
-// (archive parts -> packs cut into sequences, references as symbols) and agc_hip_sample_fasta_parts (a sample's archive parts -> its
-// FASTA text), each with its _dev twin.  The five are built from the stages below; the sample's host arithmetic is fasta_plan.h.
-// Included by api.hip behind the create path (uses its context and helpers; the kernels are lz_decode_kernels.hip,
-// fasta_out_kernels.hip, zstd_decode_kernels.hip, parts_unpack_kernels.hip).
+// (archive parts -> packs cut into sequences, references as symbols), agc_hip_sample_fasta_parts (a sample's archive parts -> its
+// FASTA text), agc_hip_lz_decode_window_batch (deltas -> a window of each one's symbols) and agc_hip_ranges_parts (archive parts -> a
+// batch of contig ranges), each with its _dev twin.  The seven are built from the stages below; the sample's host arithmetic is
+// fasta_plan.h, a range's range_plan.h.  Included by api.hip behind the create path (uses its context and helpers; the kernels are
+// lz_decode_kernels.hip, fasta_out_kernels.hip, zstd_decode_kernels.hip, parts_unpack_kernels.hip, range_kernels.hip).
 #include <map>
 
 #include "fasta_plan.h"
+#include "range_plan.h"
 
 namespace {
 
@@ -336,9 +338,109 @@ int unpack_write(agc_hip_ctx *c, std::vector<UnpackJob> &jobs, uint8_t *d_out)
     return AGC_HIP_OK;
 }
 
+// The window-write stage: lz_decode_window_kernel writes the window of every delta job (scanned, the windows inside the lengths the
+// scan reported) out of d_enc, segment_window_kernel the windows of the RAW (out of d_enc) and REF jobs, each straight to its place
+// in d_out; letters_kernel then maps the `total` symbols at d_out to letters when asked to.
+int window_write(agc_hip_ctx *c, const std::vector<WindowJob> &wj, const std::vector<WindowCopyJob> &cj, const uint8_t *d_enc, uint8_t *d_out, uint64_t total, bool letters)
+{
+    const uint32_t n_wj = (uint32_t)wj.size(), n_cj = (uint32_t)cj.size();
+    const uint32_t a = (uint32_t)((uintptr_t)d_out & (fo::CHUNK - 1));
+    const uint64_t n_chunks = fo::chunk_count(a, total), blocks = (n_chunks + 255) / 256;
+    if (blocks > 0x7FFFFFFFull) {
+        c->err = "ranges: " + std::to_string(total) + " symbols are more than one launch maps to letters";
+        return AGC_HIP_EINVAL;
+    }
+    if (n_wj) {
+        CHK(ensure(c, c->rd.d_rg_jobs, (size_t)n_wj * sizeof(WindowJob)));
+        CHK(upload(c, c->rd.d_rg_jobs.p, wj.data(), (size_t)n_wj * sizeof(WindowJob), c->stream));
+        KTimer t(c, AGC_HIP_K_RANGES);
+        hipLaunchKernelGGL(lz_decode_window_kernel, dim3((n_wj + 3) / 4), dim3(4 * WAVE), 0, c->stream, (const RefDesc *)c->d_refs.p, (const WindowJob *)c->rd.d_rg_jobs.p, n_wj,
+                           d_enc, d_out); // a wave per window
+    }
+    if (n_cj) {
+        CHK(ensure(c, c->rd.d_rg_copy, (size_t)n_cj * sizeof(WindowCopyJob)));
+        CHK(upload(c, c->rd.d_rg_copy.p, cj.data(), (size_t)n_cj * sizeof(WindowCopyJob), c->stream));
+        KTimer t(c, AGC_HIP_K_RANGES);
+        hipLaunchKernelGGL(segment_window_kernel, dim3((n_cj + 3) / 4), dim3(4 * WAVE), 0, c->stream, (const RefDesc *)c->d_refs.p, (const WindowCopyJob *)c->rd.d_rg_copy.p,
+                           n_cj, d_enc, d_out);
+    }
+    if (letters && total) {
+        KTimer t(c, AGC_HIP_K_RANGES);
+        hipLaunchKernelGGL(letters_kernel, dim3((uint32_t)blocks), dim3(256), 0, c->stream, d_out, a, total, n_chunks);
+    }
+    HIPCHK(c, hipGetLastError());
+    return AGC_HIP_OK;
+}
+
+const char *delta_refusal(uint32_t status)
+{
+    static const char *why[] = {"", "a truncated or malformed token", "'!' at or past the end of the reference", "a match outside the reference",
+                                "more than 2^32 - 1 decoded symbols"};
+    return why[status <= lzd::TOO_LONG ? status : 1];
+}
+
 const char *part_refusal(uint32_t status)
 {
     return status == pu::ZSTD_UNSUPPORTED ? "an unsupported zstd frame (status 1)" : status == pu::ZSTD_MALFORMED ? "a malformed zstd frame (status 2)" : "a malformed tuple stream (status 3)";
+}
+
+// the REF_* parts of a call are NEW references: each of a group that is not registered and that no other part names; new_ref: group ->
+// its part.  With any of them, min_match_len must be one agc_hip_ref_register takes
+int new_references(agc_hip_ctx *c, const char *call, uint32_t n_parts, const agc_hip_part *h_parts, uint32_t min_match_len, std::map<uint32_t, uint32_t> &new_ref)
+{
+    auto registered = [c](uint32_t gid) { return gid < c->refs.size() && c->refs[gid].valid; };
+    for (uint32_t i = 0; i < n_parts; ++i)
+        if (h_parts[i].content != AGC_HIP_PART_PACK) {
+            const uint32_t g = h_parts[i].gid;
+            if (registered(g) || !new_ref.emplace(g, i).second) {
+                c->err = std::string(call) + ": part " + std::to_string(i) + " is a reference of group " + std::to_string(g) + ", which " +
+                         (registered(g) ? "is registered already" : "another part is a reference of as well");
+                return AGC_HIP_EINVAL;
+            }
+        }
+    if (!new_ref.empty() && (min_match_len < HASHING_STEP + 4 || min_match_len > 32)) {
+        c->err = std::string(call) + ": a min_match_len of " + std::to_string(min_match_len) + " registers no reference";
+        return AGC_HIP_EINVAL;
+    }
+    return AGC_HIP_OK;
+}
+
+// a segment named by its part (agc_hip_seg_part's fields) against the parts; has_ref: its group is registered or among the new
+// references.  -> nullptr, or what is wrong with it (code: AGC_HIP_EINVAL / AGC_HIP_ENOREF)
+const char *seg_part_refusal(uint32_t kind, uint32_t part, uint32_t n_parts, const agc_hip_part *h_parts, bool has_ref, int &code)
+{
+    code = AGC_HIP_EINVAL;
+    if (kind > AGC_HIP_SEG_DELTA)
+        return "has an unknown kind";
+    if (kind != AGC_HIP_SEG_RAW && !has_ref) {
+        code = AGC_HIP_ENOREF;
+        return "names a group that has no registered reference and none among the parts";
+    }
+    if (kind != AGC_HIP_SEG_REF && (part >= n_parts || h_parts[part].content != AGC_HIP_PART_PACK))
+        return "names a part that is not a pack of the batch";
+    return nullptr;
+}
+
+// the new references' symbols back to back (16-byte aligned) in the context's buffer, registered in one batch from there
+int register_new_references(agc_hip_ctx *c, const PartsState &S, const std::map<uint32_t, uint32_t> &new_ref, uint32_t min_match_len)
+{
+    if (new_ref.empty())
+        return AGC_HIP_OK;
+    std::vector<UnpackJob> wj;
+    std::vector<uint32_t> gid, len;
+    std::vector<uint64_t> off;
+    uint64_t tot = 0;
+    for (const auto &gr : new_ref) {
+        const PartJob &j = S.jobs[gr.second];
+        const PartInfo &f = S.info[gr.second];
+        gid.push_back(gr.first), off.push_back(tot), len.push_back((uint32_t)f.n);
+        if (f.n)
+            wj.push_back({j.dec_off, tot, f.n, 0, f.count, 0});
+        tot += (f.n + 15) & ~(uint64_t)15;
+    }
+    CHK(ensure(c, c->rd.d_pu_out, tot + 64));
+    CHK(unpack_write(c, wj, c->rd.d_pu_out.as<uint8_t>()));
+    return agc_hip_ref_register_batch_dev(c, (uint32_t)gid.size(), gid.data(), c->rd.d_pu_out.as<uint8_t>(), off.data(), len.data(), nullptr, min_match_len);
 }
 
 } // namespace
@@ -374,9 +476,7 @@ static int lz_decode_impl(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, con
     CHK(decode_scan(c, jobs, c->rd.d_dec_enc.as<uint8_t>(), res));
     for (uint32_t i = 0; i < n; ++i)
         if (res[i].status != lzd::OK) {
-            static const char *why[] = {"", "a truncated or malformed token", "'!' at or past the end of the reference", "a match outside the reference",
-                                        "more than 2^32 - 1 decoded symbols"};
-            c->err = "lz_decode: delta " + std::to_string(i) + " is rejected: " + why[res[i].status <= lzd::TOO_LONG ? res[i].status : 1];
+            c->err = "lz_decode: delta " + std::to_string(i) + " is rejected: " + delta_refusal(res[i].status);
             return AGC_HIP_EINVAL;
         }
     uint64_t tot = 0;
@@ -557,30 +657,12 @@ static int sample_fasta_parts_impl(agc_hip_ctx *c, uint32_t n_parts, const agc_h
     CHK(parts_check(c, call, n_parts, h_parts, src_bytes));
     auto registered = [c](uint32_t gid) { return gid < c->refs.size() && c->refs[gid].valid; };
     std::map<uint32_t, uint32_t> new_ref; // group -> its part
-    for (uint32_t i = 0; i < n_parts; ++i)
-        if (h_parts[i].content != AGC_HIP_PART_PACK) {
-            const uint32_t g = h_parts[i].gid;
-            if (registered(g) || !new_ref.emplace(g, i).second) {
-                c->err = std::string(call) + ": part " + std::to_string(i) + " is a reference of group " + std::to_string(g) + ", which " +
-                         (registered(g) ? "is registered already" : "another part is a reference of as well");
-                return AGC_HIP_EINVAL;
-            }
-        }
-    if (!new_ref.empty() && (min_match_len < HASHING_STEP + 4 || min_match_len > 32)) {
-        c->err = std::string(call) + ": a min_match_len of " + std::to_string(min_match_len) + " registers no reference";
-        return AGC_HIP_EINVAL;
-    }
+    CHK(new_references(c, call, n_parts, h_parts, min_match_len, new_ref));
     const uint64_t n_seg = h_ctg_seg[n_ctg];
     for (uint64_t s = 0; s < n_seg; ++s) {
         const agc_hip_seg_part &g = h_seg[s];
-        const char *why = nullptr;
         int code = AGC_HIP_EINVAL;
-        if (g.kind > AGC_HIP_SEG_DELTA)
-            why = "has an unknown kind";
-        else if (g.kind != AGC_HIP_SEG_RAW && !registered(g.gid) && !new_ref.count(g.gid))
-            why = "names a group that has no registered reference and none among the parts", code = AGC_HIP_ENOREF;
-        else if (g.kind != AGC_HIP_SEG_REF && (g.part >= n_parts || h_parts[g.part].content != AGC_HIP_PART_PACK))
-            why = "names a part that is not a pack of the batch";
+        const char *why = seg_part_refusal(g.kind, g.part, n_parts, h_parts, registered(g.gid) || new_ref.count(g.gid), code);
         if (why) {
             c->err = std::string(call) + ": segment " + std::to_string(s) + " " + why;
             return code;
@@ -618,29 +700,213 @@ static int sample_fasta_parts_impl(agc_hip_ctx *c, uint32_t n_parts, const agc_h
         c->err = Y.why;
         return Y.code;
     }
-    // 5. the new references: their symbols back to back (16-byte aligned) in the context's buffer, registered in one batch from there
-    if (!new_ref.empty()) {
-        std::vector<UnpackJob> wj;
-        std::vector<uint32_t> gid, len;
-        std::vector<uint64_t> off;
-        uint64_t tot = 0;
-        for (const auto &gr : new_ref) {
-            const PartJob &j = S.jobs[gr.second];
-            const PartInfo &f = S.info[gr.second];
-            gid.push_back(gr.first), off.push_back(tot), len.push_back((uint32_t)f.n);
-            if (f.n)
-                wj.push_back({j.dec_off, tot, f.n, 0, f.count, 0});
-            tot += (f.n + 15) & ~(uint64_t)15;
-        }
-        CHK(ensure(c, c->rd.d_pu_out, tot + 64));
-        CHK(unpack_write(c, wj, c->rd.d_pu_out.as<uint8_t>()));
-        CHK(agc_hip_ref_register_batch_dev(c, (uint32_t)gid.size(), gid.data(), c->rd.d_pu_out.as<uint8_t>(), off.data(), len.data(), nullptr, min_match_len));
-    }
+    // 5. the new references, registered in one batch from the device buffer
+    CHK(register_new_references(c, S, new_ref, min_match_len));
     // 6. agc_hip_sample_fasta's path, the deltas and raw symbols read where the parts stage left them
     return write_sample(c, Y, c->rd.d_pu_dec.as<uint8_t>(), n_ctg, h_ctg_seg, h_names, h_name_off, line_length, h_text, d_text, T);
 }
 
+// The windowed LZ decode: the output's layout follows from the windows' sizes, so the capacity is looked at first; the scan stage
+// then checks every delta and says how long it is, and only when every window lies inside its delta is anything written.
+static int lz_decode_window_impl(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const uint8_t *h_enc, const uint64_t *h_enc_off, const uint8_t *h_rc,
+                                 const uint32_t *h_win_from, const uint32_t *h_win_len, uint8_t *h_out, uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_off)
+{
+    static const char *call = "lz_decode_window";
+    if (!c || !h_out_off || (n && (!h_gid || !h_enc_off || !h_win_from || !h_win_len || (h_enc_off[n] > h_enc_off[0] && !h_enc))) || (out_cap && !h_out && !d_out))
+        return AGC_HIP_EINVAL;
+    h_out_off[0] = 0;
+    if (!n)
+        return AGC_HIP_OK;
+    uint64_t tot = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        h_out_off[i] = tot;
+        tot += h_win_len[i];
+    }
+    h_out_off[n] = tot;
+    CHK(capacity_holds(c, call, "output", out_cap, tot));
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!h_win_len[i]) {
+            c->err = std::string(call) + ": delta " + std::to_string(i) + " has a window of no symbols";
+            return AGC_HIP_EINVAL;
+        }
+        if (h_gid[i] >= c->refs.size() || !c->refs[h_gid[i]].valid) {
+            c->err = std::string(call) + ": delta " + std::to_string(i) + ": group " + std::to_string(h_gid[i]) + " has no registered reference";
+            return AGC_HIP_EINVAL;
+        }
+        CHK(offsets_ascend(c, call, "delta", h_enc_off, i));
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(upload_refs(c));
+    const uint64_t e0 = h_enc_off[0], enc_bytes = h_enc_off[n] - e0;
+    std::vector<DecodeJob> jobs(n);
+    for (uint32_t i = 0; i < n; ++i)
+        jobs[i] = {h_enc_off[i] - e0, h_enc_off[i + 1] - h_enc_off[i], 0, 0, h_gid[i], h_rc && h_rc[i] ? 1u : 0u, 0};
+    CHK(ensure(c, c->rd.d_dec_enc, enc_bytes + 64));
+    if (enc_bytes)
+        CHK(upload(c, c->rd.d_dec_enc.p, h_enc + e0, enc_bytes, c->stream));
+    std::vector<DecodeResult> res;
+    CHK(decode_scan(c, jobs, c->rd.d_dec_enc.as<uint8_t>(), res));
+    std::vector<WindowJob> wj(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (res[i].status != lzd::OK) {
+            c->err = std::string(call) + ": delta " + std::to_string(i) + " is rejected: " + delta_refusal(res[i].status);
+            return AGC_HIP_EINVAL;
+        }
+        if (!rp::window_fits(h_win_from[i], h_win_len[i], res[i].len)) {
+            c->err = std::string(call) + ": delta " + std::to_string(i) + " decodes to " + std::to_string(res[i].len) + " symbols, its window [" +
+                     std::to_string(h_win_from[i]) + ", +" + std::to_string(h_win_len[i]) + ") reaches past them";
+            return AGC_HIP_EINVAL;
+        }
+        wj[i] = {jobs[i].enc_off, jobs[i].enc_len, h_out_off[i], 0, 0, jobs[i].ref_slot, jobs[i].rc};
+        rw::decode_window(h_win_from[i], h_win_len[i], res[i].len, jobs[i].rc, wj[i].w_lo, wj[i].w_hi);
+    }
+    CHK(output_buffer(c, d_out, c->rd.d_rg_out, tot));
+    CHK(window_write(c, wj, {}, c->rd.d_dec_enc.as<uint8_t>(), d_out, tot, false));
+    return hand_back(c, h_out, d_out, tot);
+}
+
+// A batch of contig ranges from their archive parts: agc_hip_sample_fasta_parts's order of events (include/agc_hip.h) with windows in
+// the place of whole segments -- everything the host can refuse is refused before the references are registered; behind the
+// registration only the deltas themselves can still be refused.
+static int ranges_parts_impl(agc_hip_ctx *c, uint32_t n_parts, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap, uint32_t n_q,
+                             const uint64_t *h_q_seg, const agc_hip_seg_win *h_win, uint32_t min_match_len, int letters, uint8_t *h_out, uint8_t *d_out, uint64_t out_cap,
+                             uint64_t *h_out_off)
+{
+    static const char *call = "ranges_parts";
+    if (!c || !h_out_off || (n_q && (!h_q_seg || (h_q_seg[n_q] && !h_win))) || (n_parts && (!h_parts || (src_bytes && !h_src))) || (out_cap && !h_out && !d_out))
+        return AGC_HIP_EINVAL;
+    h_out_off[0] = 0;
+    if (!n_q)
+        return AGC_HIP_OK;
+    // 1. the output's layout
+    const uint64_t n_win = h_q_seg[n_q];
+    bool ascending = h_q_seg[0] == 0 && n_win <= 0xFFFFFFFFull;
+    for (uint32_t q = 0; q < n_q; ++q)
+        ascending = ascending && h_q_seg[q] <= h_q_seg[q + 1] && h_q_seg[q + 1] <= n_win;
+    if (!ascending) {
+        c->err = std::string(call) + ": the queries' window ranges do not ascend from 0";
+        return AGC_HIP_EINVAL;
+    }
+    std::vector<uint64_t> win_out(n_win); // where every window goes
+    uint64_t tot = 0;
+    for (uint32_t q = 0; q < n_q; ++q) {
+        h_out_off[q] = tot;
+        for (uint64_t w = h_q_seg[q]; w < h_q_seg[q + 1]; ++w) {
+            win_out[w] = tot;
+            tot += h_win[w].win_len;
+        }
+    }
+    h_out_off[n_q] = tot;
+    CHK(capacity_holds(c, call, "output", out_cap, tot));
+    // 2. the plan against the parts and the context
+    CHK(parts_check(c, call, n_parts, h_parts, src_bytes));
+    auto registered = [c](uint32_t gid) { return gid < c->refs.size() && c->refs[gid].valid; };
+    std::map<uint32_t, uint32_t> new_ref; // group -> its part
+    CHK(new_references(c, call, n_parts, h_parts, min_match_len, new_ref));
+    for (uint64_t w = 0; w < n_win; ++w) {
+        const agc_hip_seg_win &g = h_win[w];
+        int code = AGC_HIP_EINVAL;
+        const char *why = seg_part_refusal(g.kind, g.part, n_parts, h_parts, registered(g.gid) || new_ref.count(g.gid), code);
+        if (!why && !rp::window_fits(g.win_from, g.win_len, g.length))
+            why = g.win_len ? "reaches past its segment's length" : "has no symbols";
+        if (why) {
+            c->err = std::string(call) + ": window " + std::to_string(w) + " " + why;
+            return code;
+        }
+    }
+    if (!n_win)
+        return AGC_HIP_OK;
+    // 3. the parts, unpacked on the device
+    HIPCHK(c, hipSetDevice(c->device));
+    PartsState S;
+    if (n_parts)
+        CHK(parts_decode_index(c, n_parts, h_parts, h_src, seq_cap, S));
+    // 4. what the device found, against the plan -- nothing is registered or written yet
+    for (uint32_t i = 0; i < n_parts; ++i)
+        if (S.status(i) != pu::OK || (h_parts[i].content != AGC_HIP_PART_PACK && S.info[i].n > 0xFFFFFFFFull)) {
+            c->err = std::string(call) + ": part " + std::to_string(i) + " is refused: " + (S.status(i) != pu::OK ? part_refusal(S.status(i)) : "a reference of 2^32 symbols or more");
+            return AGC_HIP_EINVAL;
+        }
+    std::vector<DecodeJob> dj;
+    std::vector<WindowJob> wj;
+    std::vector<uint64_t> dj_win;
+    std::vector<WindowCopyJob> cj;
+    for (uint64_t w = 0; w < n_win; ++w) {
+        const agc_hip_seg_win &g = h_win[w];
+        const uint32_t rc = g.rc ? 1u : 0u;
+        uint64_t off = 0;
+        uint32_t n = 0;
+        if (g.kind != AGC_HIP_SEG_REF) {
+            if (g.index >= S.info[g.part].count || g.index >= seq_cap) {
+                c->err = std::string(call) + ": window " + std::to_string(w) + " is of sequence " + std::to_string(g.index) + " of part " + std::to_string(g.part) +
+                         ", which has " + std::to_string(S.info[g.part].count) + " (at most " + std::to_string(seq_cap) + " are indexed)";
+                return AGC_HIP_EINVAL;
+            }
+            S.sequence(g.part, g.index, off, n);
+        }
+        if (g.kind == AGC_HIP_SEG_DELTA) {
+            dj.push_back({off, n, 0, g.length, g.gid, rc, 0});
+            dj_win.push_back(w);
+            WindowJob j = {off, n, win_out[w], 0, 0, g.gid, rc};
+            rw::decode_window(g.win_from, g.win_len, g.length, rc, j.w_lo, j.w_hi);
+            wj.push_back(j);
+            continue;
+        }
+        const auto it = new_ref.find(g.gid);
+        const uint64_t have = g.kind == AGC_HIP_SEG_RAW ? n : it != new_ref.end() ? S.info[it->second].n : c->refs[g.gid].ref_size;
+        if (have != g.length) {
+            c->err = std::string(call) + ": window " + std::to_string(w) + " is of a " + (g.kind == AGC_HIP_SEG_RAW ? "raw sequence" : "reference") + " of " +
+                     std::to_string(have) + " symbols, its length says " + std::to_string(g.length);
+            return AGC_HIP_EINVAL;
+        }
+        cj.push_back({off, win_out[w], g.length, g.win_from, g.win_len, g.gid, rc, g.kind == AGC_HIP_SEG_REF ? 1u : 0u});
+    }
+    // 5. the new references, registered in one batch from the device buffer
+    CHK(register_new_references(c, S, new_ref, min_match_len));
+    // 6. the deltas against their lengths, then every window to its place
+    CHK(upload_refs(c));
+    const uint8_t *d_bytes = c->rd.d_pu_dec.as<uint8_t>();
+    if (!dj.empty()) {
+        std::vector<DecodeResult> res;
+        CHK(decode_scan(c, dj, d_bytes, res));
+        for (size_t i = 0; i < dj.size(); ++i)
+            if (res[i].status != lzd::OK || res[i].len != dj[i].out_len) {
+                c->err = std::string(call) + ": window " + std::to_string(dj_win[i]) +
+                         (res[i].status != lzd::OK ? " is of a malformed delta" : " is of a delta that decodes to " + std::to_string(res[i].len) + " symbols, its length says " + std::to_string(dj[i].out_len));
+                return AGC_HIP_EINVAL;
+            }
+    }
+    CHK(output_buffer(c, d_out, c->rd.d_rg_out, tot));
+    CHK(window_write(c, wj, cj, d_bytes, d_out, tot, letters != 0));
+    return hand_back(c, h_out, d_out, tot);
+}
+
 extern "C" {
+
+int agc_hip_lz_decode_window_batch(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const uint8_t *h_enc, const uint64_t *h_enc_off, const uint8_t *h_rc,
+                                   const uint32_t *h_win_from, const uint32_t *h_win_len, uint8_t *h_out, uint64_t out_cap, uint64_t *h_out_off)
+{
+    return lz_decode_window_impl(c, n, h_gid, h_enc, h_enc_off, h_rc, h_win_from, h_win_len, h_out, nullptr, out_cap, h_out_off);
+}
+
+int agc_hip_lz_decode_window_batch_dev(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const uint8_t *h_enc, const uint64_t *h_enc_off, const uint8_t *h_rc,
+                                       const uint32_t *h_win_from, const uint32_t *h_win_len, uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_off)
+{
+    return lz_decode_window_impl(c, n, h_gid, h_enc, h_enc_off, h_rc, h_win_from, h_win_len, nullptr, d_out, out_cap, h_out_off);
+}
+
+int agc_hip_ranges_parts(agc_hip_ctx *c, uint32_t n_parts, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap, uint32_t n_q,
+                         const uint64_t *h_q_seg, const agc_hip_seg_win *h_win, uint32_t min_match_len, int letters, uint8_t *h_out, uint64_t out_cap, uint64_t *h_out_off)
+{
+    return ranges_parts_impl(c, n_parts, h_parts, h_src, src_bytes, seq_cap, n_q, h_q_seg, h_win, min_match_len, letters, h_out, nullptr, out_cap, h_out_off);
+}
+
+int agc_hip_ranges_parts_dev(agc_hip_ctx *c, uint32_t n_parts, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap, uint32_t n_q,
+                             const uint64_t *h_q_seg, const agc_hip_seg_win *h_win, uint32_t min_match_len, int letters, uint8_t *d_out, uint64_t out_cap,
+                             uint64_t *h_out_off)
+{
+    return ranges_parts_impl(c, n_parts, h_parts, h_src, src_bytes, seq_cap, n_q, h_q_seg, h_win, min_match_len, letters, nullptr, d_out, out_cap, h_out_off);
+}
 
 int agc_hip_lz_decode_batch(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const uint8_t *h_enc, const uint64_t *h_enc_off, const uint8_t *h_rc,
                             uint8_t *h_out, uint64_t out_cap, uint64_t *h_out_off)

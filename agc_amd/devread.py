@@ -1,4 +1,4 @@
-"""A sample's FASTA text written on the GPU.  Two ways in, the same text out:
+"""A sample's FASTA text, and batches of contig ranges, written on the GPU.  A sample's text has two ways in, the same text out:
 
 sample_fasta / sample_fasta_dev: the host reader opens the archive and decodes the zstd parts (agc_amd/reader.py, libagc_read.so),
 everything behind that -- the LZ-diff decode, orientation, the k-symbol overlap, the alphabet and the line wrapping -- is one call
@@ -8,11 +8,18 @@ sample_fasta_parts / sample_fasta_parts_dev: the host reader only reads the coll
 sample needs (GetSampleParts); their bytes go to the device as the archive holds them and are zstd-decoded, cut into sequences,
 un-tupled and -- the references not registered yet -- registered there (agc_hip_sample_fasta_parts).
 
+ranges / ranges_dev: a batch of windows (sample, contig, start, end) -- the range as GetCtgSeq reads it: inclusive, -1 / -1 the whole
+contig -- through the same parts path: the host reader says which segments each range touches, which window of each, and which
+stored parts the whole batch needs (GetRangeParts); the device decodes those parts and writes every window straight to its place
+(agc_hip_ranges_parts).  No whole segment and no whole sample is materialised.
+
     ctx = capi.Context(0)
     r = DeviceReader(ctx, "collection.agc")
     text = r.sample_fasta("HG00438.1")          # bytes, what `agc getset` writes
     d = r.sample_fasta_dev("HG00438.1")         # the same as a torch uint8 tensor on the device
     text = r.sample_fasta_parts("HG00438.1")    # the same bytes, nothing but metadata decoded on the host
+    seqs = r.ranges([("HG00438.1", "chr1", 1000, 1999), (None, "chrM", -1, -1)])   # a list of bytes: letters, one per query
+    d, off = r.ranges_dev(queries, letters=False)                                  # symbol codes on the device, query q = d[off[q]:off[q+1]]
     r.close()
 
 Group references are registered with the context once, as gid_base + group id: two readers on one context need disjoint ranges.
@@ -137,3 +144,50 @@ class DeviceReader:
             rc, _n = self.ctx.sample_fasta_parts_raw(*args, line_length, names, name_off, out.data_ptr(), need, dev=True)
             self._after(rc, new)
         return out
+
+    def range_parts(self, queries):
+        """the batch's windows and stored parts (reader.CAGCFile.GetRangeParts, without the references registered already) -> (the
+        arguments of Context.ranges_parts_raw in front of `letters`, the groups whose references are among the parts).  An unknown or
+        ambiguous contig raises KeyError naming the first such query"""
+        if self.file is None:
+            raise RuntimeError("the reader is closed")
+        p = self.file.GetRangeParts(queries, self.registered)
+        if p is None:
+            raise RuntimeError("the archive does not hold a part the ranges need")
+        is_ref = p["part_content"] != reader.PART_PACK
+        parts = np.zeros(p["part_off"].size, capi.PART_DTYPE)
+        parts["off"], parts["n_bytes"], parts["coding"], parts["content"] = p["part_off"], p["part_bytes"], p["part_coding"], p["part_content"]
+        parts["gid"] = np.where(is_ref, p["part_group"] + np.uint32(self.gid_base), 0)
+        wins = np.zeros(p["kind"].size, capi.SEG_WIN_DTYPE)
+        wins["kind"] = p["kind"]
+        wins["gid"] = np.where(p["kind"] == capi.SEG_RAW, 0, p["group_id"] + np.uint32(self.gid_base))
+        wins["part"], wins["index"], wins["length"], wins["rc"] = p["seg_part"], p["seg_index"], p["length"], p["rc"]
+        wins["win_from"], wins["win_len"] = p["win_from"], p["win_len"]
+        args = (parts, (p["src"], p["src_bytes"]), self.pack_cardinality, p["q_seg"], wins, self.min_match_len)
+        return args, p["part_group"][is_ref].tolist()
+
+    def ranges(self, queries, letters=True):
+        """queries: a sequence of (sample, contig, start, end), sample may be None -> a list of bytes, one per query: the letters
+        GetCtgSeq returns (letters=False: the symbol codes)"""
+        args, new = self.range_parts(queries)
+        rc, off = self.ctx.ranges_parts_raw(*args, letters, self._pinned, self._pinned_cap)
+        if rc == capi.ECAP:  # (the output's size follows from the windows: nothing was launched or registered)
+            rc, off = self.ctx.ranges_parts_raw(*args, letters, self._pinned_buffer(int(off[-1])), self._pinned_cap)
+        self._after(rc, new)
+        data = C.string_at(self._pinned, int(off[-1])) if int(off[-1]) else b""
+        return [data[int(off[q]):int(off[q + 1])] for q in range(off.size - 1)]
+
+    def ranges_dev(self, queries, letters=True):
+        """-> (the same symbols back to back as a torch uint8 tensor on the context's device, the queries' offsets in it: numpy uint64,
+        n_q + 1)"""
+        import torch
+        args, new = self.range_parts(queries)
+        rc, off = self.ctx.ranges_parts_raw(*args, letters, None, 0, dev=True)
+        if rc != capi.ECAP:
+            self._after(rc, new)
+        out = torch.empty(int(off[-1]), dtype=torch.uint8, device="cuda")
+        if int(off[-1]):
+            torch.cuda.synchronize()
+            rc, off = self.ctx.ranges_parts_raw(*args, letters, out.data_ptr(), int(off[-1]), dev=True)
+            self._after(rc, new)
+        return out, off

@@ -11,7 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libagc_read.so")
 SYMBOLS = ["agc_open", "agc_close", "agc_get_ctg_len", "agc_get_ctg_seq", "agc_n_sample", "agc_n_ctg", "agc_reference_sample",
            "agc_list_sample", "agc_list_ctg", "agc_list_destroy", "agc_string_destroy", "agc_get_sample_fasta", "agc_get_params",
-           "agc_get_sample_plan", "agc_plan_fields", "agc_plan_destroy", "agc_get_sample_parts", "agc_parts_fields", "agc_parts_destroy"]
+           "agc_get_sample_plan", "agc_plan_fields", "agc_plan_destroy", "agc_get_sample_parts", "agc_parts_fields", "agc_parts_destroy",
+           "agc_get_range_parts", "agc_ranges_fields", "agc_ranges_destroy"]
 PLAN_RAW, PLAN_REF, PLAN_DELTA = 0, 1, 2
 PART_STORED, PART_ZSTD = 0, 1
 PART_PACK, PART_REF_BYTES, PART_REF_TUPLES = 0, 1, 2
@@ -35,7 +36,27 @@ class PartsView(C.Structure):
                 ("part_off", _u64p), ("part_bytes", _u32p), ("part_coding", _u32p), ("part_content", _u32p), ("part_group", _u32p), ("part_no", _u32p)]
 
 
+class RangesView(C.Structure):
+    """agc_ranges_view (include/agc_read.h)"""
+    _u32p, _u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+    _fields_ = [("n_q", C.c_uint64), ("n_win", C.c_uint64), ("n_parts", C.c_uint64), ("src_bytes", C.c_uint64), ("src", C.c_void_p),
+                ("q_seg", _u64p), ("q_len", _u64p),
+                ("group_id", _u32p), ("in_group_id", _u32p), ("rc", _u32p), ("length", _u32p), ("kind", _u32p), ("seg_part", _u32p), ("seg_index", _u32p),
+                ("win_from", _u32p), ("win_len", _u32p),
+                ("part_off", _u64p), ("part_bytes", _u32p), ("part_coding", _u32p), ("part_content", _u32p), ("part_group", _u32p), ("part_no", _u32p)]
+
+
 _lib = None
+
+
+def _arr(ptr, n, dt):
+    """n items of type dt at ptr (an address or a ctypes pointer) as a numpy array of its own"""
+    import numpy as np
+    n = int(n)
+    if not n:
+        return np.zeros(0, dt)
+    addr = ptr if isinstance(ptr, int) else C.addressof(ptr.contents)
+    return np.frombuffer((C.c_char * (n * np.dtype(dt).itemsize)).from_address(addr), dtype=dt).copy()
 
 
 def load():
@@ -72,6 +93,11 @@ def load():
     L.agc_get_sample_parts.argtypes = [vp, cp, C.POINTER(C.c_uint32), C.c_uint64]
     L.agc_parts_fields.argtypes = [vp, C.POINTER(PartsView)]
     L.agc_parts_destroy.argtypes = [vp]
+    L.agc_get_range_parts.restype = vp
+    L.agc_get_range_parts.argtypes = [vp, C.c_uint64, C.POINTER(cp), C.POINTER(cp), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.c_uint64,
+                                      C.POINTER(C.c_int64)]
+    L.agc_ranges_fields.argtypes = [vp, C.POINTER(RangesView)]
+    L.agc_ranges_destroy.argtypes = [vp]
     _lib = L
     return L
 
@@ -188,13 +214,7 @@ class CAGCFile:
             v = PlanView()
             if self.L.agc_plan_fields(h, C.byref(v)) != 0:
                 return None
-
-            def arr(ptr, n, dt):
-                n = int(n)
-                if not n:
-                    return np.zeros(0, dt)
-                addr = ptr if isinstance(ptr, int) else C.addressof(ptr.contents)
-                return np.frombuffer((C.c_char * (n * np.dtype(dt).itemsize)).from_address(addr), dtype=dt).copy()
+            arr = _arr
 
             out = {"name_off": arr(v.name_off, v.n_ctg + 1, np.uint64), "ctg_seg": arr(v.ctg_seg, v.n_ctg + 1, np.uint64)}
             out["names"] = arr(v.names, out["name_off"][-1], np.uint8).tobytes()
@@ -224,13 +244,7 @@ class CAGCFile:
             v = PartsView()
             if self.L.agc_parts_fields(h, C.byref(v)) != 0:
                 return None
-
-            def arr(ptr, n, dt):
-                n = int(n)
-                if not n:
-                    return np.zeros(0, dt)
-                addr = ptr if isinstance(ptr, int) else C.addressof(ptr.contents)
-                return np.frombuffer((C.c_char * (n * np.dtype(dt).itemsize)).from_address(addr), dtype=dt).copy()
+            arr = _arr
 
             out = {"name_off": arr(v.name_off, v.n_ctg + 1, np.uint64), "ctg_seg": arr(v.ctg_seg, v.n_ctg + 1, np.uint64)}
             out["names"] = arr(v.names, out["name_off"][-1], np.uint8).tobytes()
@@ -244,3 +258,43 @@ class CAGCFile:
             return out
         finally:
             self.L.agc_parts_destroy(h)
+
+    def GetRangeParts(self, queries, have=()):
+        """the windows and stored parts of a batch of contig ranges (agc_get_range_parts) as numpy arrays of their own.  queries: a
+        sequence of (sample, contig, start, end) -- sample None or "": the contig name must be unique; the range as GetCtgSeq reads it.
+        -> q_seg (n_q + 1) / q_len (n_q), per window entry group_id / in_group_id / rc / length / kind (PLAN_*) / seg_part / seg_index
+        / win_from / win_len, the parts and src / src_bytes / part(i) as GetSampleParts has them (each part once for the whole batch).
+        An unknown or ambiguous contig raises KeyError(the index of the first such query, the query)"""
+        import numpy as np
+        if not self.h:
+            return None
+        qs = list(queries)
+        n = len(qs)
+        smp = (C.c_char_p * max(n, 1))(*[q[0].encode() if q[0] else None for q in qs])
+        nam = (C.c_char_p * max(n, 1))(*[q[1].encode() for q in qs])
+        frm = np.ascontiguousarray([int(q[2]) for q in qs], dtype=np.int64)
+        to = np.ascontiguousarray([int(q[3]) for q in qs], dtype=np.int64)
+        hv = np.ascontiguousarray(sorted(int(g) for g in have), dtype=np.uint32)
+        bad = C.c_int64(-1)
+        i64p = C.POINTER(C.c_int64)
+        h = self.L.agc_get_range_parts(self.h, n, smp, nam, frm.ctypes.data_as(i64p), to.ctypes.data_as(i64p), hv.ctypes.data_as(C.POINTER(C.c_uint32)), hv.size,
+                                       C.byref(bad))
+        if not h:
+            if bad.value >= 0:
+                raise KeyError(bad.value, tuple(qs[bad.value]))
+            return None
+        try:
+            v = RangesView()
+            if self.L.agc_ranges_fields(h, C.byref(v)) != 0:
+                return None
+            out = {"q_seg": _arr(v.q_seg, v.n_q + 1, np.uint64), "q_len": _arr(v.q_len, v.n_q, np.uint64)}
+            for f in ("group_id", "in_group_id", "rc", "length", "kind", "seg_part", "seg_index", "win_from", "win_len"):
+                out[f] = _arr(getattr(v, f), v.n_win, np.uint32)
+            out["part_off"] = _arr(v.part_off, v.n_parts, np.uint64)
+            for f in ("part_bytes", "part_coding", "part_content", "part_group", "part_no"):
+                out[f] = _arr(getattr(v, f), v.n_parts, np.uint32)
+            out["src"], out["src_bytes"] = v.src, int(v.src_bytes)
+            out["part"] = lambda i: C.string_at(out["src"] + int(out["part_off"][i]), int(out["part_bytes"][i]))
+            return out
+        finally:
+            self.L.agc_ranges_destroy(h)

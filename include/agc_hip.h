@@ -65,7 +65,8 @@ enum {
     AGC_HIP_K_FASTA_OUT = 14,    /* agc_hip_sample_fasta*: segment_copy_kernel + fasta_text_kernel (fasta_out_kernels.hip) */
     AGC_HIP_K_ZSTD_DECODE = 15,  /* agc_hip_zstd_decode_batch*: zstd_decode_kernel (zstd_decode_kernels.hip) */
     AGC_HIP_K_PARTS_UNPACK = 16, /* agc_hip_parts_unpack*, agc_hip_sample_fasta_parts*: pack_index_kernel, tuples_size_kernel, tuples_unpack_kernel (parts_unpack_kernels.hip) */
-    AGC_HIP_K_COUNT = 17
+    AGC_HIP_K_RANGES = 17,       /* agc_hip_lz_decode_window_batch*, agc_hip_ranges_parts*: lz_decode_window_kernel, segment_window_kernel, letters_kernel (range_kernels.hip) */
+    AGC_HIP_K_COUNT = 18
 };
 int agc_hip_timing_enable(agc_hip_ctx *ctx, int on);
 int agc_hip_timing_reset(agc_hip_ctx *ctx);
@@ -335,6 +336,21 @@ int agc_hip_lz_decode_batch(agc_hip_ctx *ctx, uint32_t n, const uint32_t *h_gid,
 int agc_hip_lz_decode_batch_dev(agc_hip_ctx *ctx, uint32_t n, const uint32_t *h_gid, const uint8_t *h_enc, const uint64_t *h_enc_off,
                                 const uint8_t *h_rc, uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_off);
 
+/* The same decode for a WINDOW of every delta: of the oriented symbols delta s decodes to (reverse-complemented when h_rc && h_rc[s])
+ * only [h_win_from[s], h_win_from[s] + h_win_len[s]) is written, h_win_len[s] >= 1; the whole segment is never materialised.
+ * Output s = out[h_out_off[s] .. h_out_off[s+1]), exactly h_win_len[s] bytes: the offsets follow from the arguments, so
+ * AGC_HIP_ECAP (out_cap too small; h_out_off[0..n] filled) comes before any launch.  AGC_HIP_EINVAL, nothing written to out, the
+ * error text naming the first offender: a window of no symbols (before any launch), an unknown gid, a malformed delta (the rules
+ * above), a window that reaches past its delta's decoded length (found by the scan that checks the deltas).  Runs on the context's
+ * first stream. */
+int agc_hip_lz_decode_window_batch(agc_hip_ctx *ctx, uint32_t n, const uint32_t *h_gid, const uint8_t *h_enc, const uint64_t *h_enc_off,
+                                   const uint8_t *h_rc, const uint32_t *h_win_from, const uint32_t *h_win_len, uint8_t *h_out, uint64_t out_cap,
+                                   uint64_t *h_out_off);
+/* the same, the windows left in device memory (d_out: out_cap bytes the caller owns, any alignment) */
+int agc_hip_lz_decode_window_batch_dev(agc_hip_ctx *ctx, uint32_t n, const uint32_t *h_gid, const uint8_t *h_enc, const uint64_t *h_enc_off,
+                                       const uint8_t *h_rc, const uint32_t *h_win_from, const uint32_t *h_win_len, uint8_t *d_out, uint64_t out_cap,
+                                       uint64_t *h_out_off);
+
 /* ---- the read side behind zstd: a sample's FASTA text ------------------------------------------------------ */
 /* Where the symbols of one segment of a contig come from.  RAW: symbol bytes the caller supplies (the raw groups, ids < 16:
  * CSegment::get_raw, src/common/segment.cpp:136-215); REF: the registered reference of a group as it is (in_group_id 0 of a group
@@ -595,6 +611,46 @@ int agc_hip_sample_fasta_parts_dev(agc_hip_ctx *ctx, uint32_t n_parts, const agc
                                    uint32_t n_ctg, const uint64_t *h_ctg_seg, const agc_hip_seg_part *h_seg, uint32_t k, uint32_t min_match_len,
                                    uint32_t line_length, const char *h_names, const uint64_t *h_name_off, uint8_t *d_text, uint64_t text_cap,
                                    uint64_t *h_text_len);
+
+/* One window of a batch of contig ranges: the segment as agc_hip_seg_part names it, and the symbols [win_from, win_from + win_len)
+ * of its ORIENTED form (win_len >= 1, win_from + win_len <= length).  The k-symbol overlap between segments is the caller's to
+ * account for in win_from (include/agc_read.h: agc_get_range_parts does). */
+typedef struct {
+    uint32_t kind;   /* AGC_HIP_SEG_* */
+    uint32_t gid;    /* REF, DELTA */
+    uint32_t part;   /* RAW, DELTA */
+    uint32_t index;
+    uint32_t length;
+    uint32_t rc;
+    uint32_t win_from;
+    uint32_t win_len;
+} agc_hip_seg_win;
+
+/* A batch of contig ranges from the archive's parts.  Query q is the windows h_win[h_q_seg[q] .. h_q_seg[q+1]) back to back: it is
+ * written to out[h_out_off[q] .. h_out_off[q+1]), every window straight to its place, as symbol codes (letters == 0) or as the
+ * letters "ACGTNRYSWKMBDHVU" (letters != 0).  h_parts / h_src / src_bytes / seq_cap / min_match_len as agc_hip_sample_fasta_parts
+ * takes them: every REF_* part is a NEW reference, registered under its gid.  In this order:
+ *  1. h_out_off[0..n_q] from the windows' sizes alone.  AGC_HIP_ECAP: out_cap is smaller than h_out_off[n_q]; nothing was launched.
+ *     AGC_HIP_EINVAL with nothing but h_out_off[0] = 0 filled: an h_q_seg that does not ascend from 0, a NULL that is needed.
+ *  2. Refused before any launch: what step 2 of agc_hip_sample_fasta_parts refuses, and a window with win_len == 0 or
+ *     win_from + win_len > length (AGC_HIP_EINVAL).  A batch without a window ends here with AGC_HIP_OK: nothing is unpacked or
+ *     registered.
+ *  3. The parts are unpacked on the device; counts, end offsets, reference sizes and statuses come back in one copy.
+ *  4. AGC_HIP_EINVAL, the error text naming the part or window: a refused part; an index at or above its pack's count (or above
+ *     seq_cap); a RAW whose sequence, or a REF whose reference, has another size than `length`.  NO reference has been registered,
+ *     nothing has been written to out: the context is as it was.
+ *  5. The new references are registered in one batch, from the device buffer.
+ *  6. The deltas are scanned; a malformed one, or one that decodes to another size than `length`, is refused (AGC_HIP_EINVAL,
+ *     nothing written to out) -- which does NOT undo step 5: the new references stay registered and valid, and a caller must not
+ *     hand their parts in again.  Then the windows are written, and mapped to letters when asked for.
+ * No pack byte and no reference symbol goes back to the host.  Runs on the context's first stream. */
+int agc_hip_ranges_parts(agc_hip_ctx *ctx, uint32_t n_parts, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap,
+                         uint32_t n_q, const uint64_t *h_q_seg, const agc_hip_seg_win *h_win, uint32_t min_match_len, int letters, uint8_t *h_out,
+                         uint64_t out_cap, uint64_t *h_out_off);
+/* the same, the symbols left in device memory (d_out: out_cap bytes the caller owns, any alignment) */
+int agc_hip_ranges_parts_dev(agc_hip_ctx *ctx, uint32_t n_parts, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap,
+                             uint32_t n_q, const uint64_t *h_q_seg, const agc_hip_seg_win *h_win, uint32_t min_match_len, int letters, uint8_t *d_out,
+                             uint64_t out_cap, uint64_t *h_out_off);
 
 #ifdef __cplusplus
 }

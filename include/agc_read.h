@@ -106,6 +106,35 @@ int agc_parts_fields(const agc_parts_t *parts, agc_parts_view *out);
 /* frees the parts object (NULL: nothing to do); returns 0 */
 int agc_parts_destroy(agc_parts_t *parts);
 
+/* extension: the stored parts a BATCH of contig ranges needs, for a caller that decodes elsewhere (agc_amd/devread.py: on the GPU,
+ * include/agc_hip.h: agc_hip_ranges_parts).  Query q is contig names[q] of samples[q] -- full or short name; samples NULL, or
+ * samples[q] NULL or empty: the name must be unique in the archive -- positions [from[q], to[q]] inclusive, read as agc_get_ctg_seq
+ * reads them: from < 0 is 0, to < 0 is the contig's end, from > to is the whole contig, everything is clamped to the contig; a range
+ * that starts at or behind the contig's end is a valid query of no symbols.  Query q yields q_len[q] symbols and owns the window
+ * entries [q_seg[q], q_seg[q+1]): one per segment that contributes at least one symbol, with the segment's fields as in
+ * agc_parts_view and the window [win_from, win_from + win_len) of its ORIENTED symbols (win_len >= 1; the k-symbol overlap is
+ * accounted for: behind a contig's first segment win_from >= k).  A query's windows back to back, in entry order, are its symbols.
+ * The parts: the distinct parts of the whole batch, each once, in the order and with the fields of agc_get_sample_parts (new
+ * references ascending by group -- those of have_groups left out -- then packs).  Nothing is decompressed and none of the reader's
+ * caches is touched.  NULL: an unknown or ambiguous contig -- *bad_query (may be NULL) = the first such query -- or a part the
+ * archive does not hold, a NULL that is needed (*bad_query = -1). */
+typedef struct agc_ranges_t agc_ranges_t;
+typedef struct {
+    uint64_t n_q, n_win, n_parts, src_bytes;
+    const uint8_t *src;
+    const uint64_t *q_seg; /* n_q + 1 */
+    const uint64_t *q_len; /* n_q */
+    const uint32_t *group_id, *in_group_id, *rc, *length, *kind, *seg_part, *seg_index, *win_from, *win_len; /* n_win each */
+    const uint64_t *part_off;                                                                                  /* n_parts */
+    const uint32_t *part_bytes, *part_coding, *part_content, *part_group, *part_no;                            /* n_parts each */
+} agc_ranges_view;
+agc_ranges_t *agc_get_range_parts(const agc_t *agc, uint64_t n_q, const char *const *samples, const char *const *names, const int64_t *from, const int64_t *to,
+                                  const uint32_t *have_groups, uint64_t n_have, int64_t *bad_query);
+/* fills *out; 0 for success */
+int agc_ranges_fields(const agc_ranges_t *ranges, agc_ranges_view *out);
+/* frees the ranges object (NULL: nothing to do); returns 0 */
+int agc_ranges_destroy(agc_ranges_t *ranges);
+
 #ifdef __cplusplus
 }
 #endif
