@@ -16,7 +16,7 @@ OK, ENODEV, EINVAL, ENOMEM, ECAP, ENOREF = 0, -1, -2, -3, -4, -5
 K_SCAN, K_INDEX, K_ENCODE, K_ESTIMATE, K_COSTVEC, K_REVCOMP, K_PREPROCESS, K_REFSTORE = range(8)
 K_NAMES = ["scan", "index", "encode", "estimate", "costvec", "revcomp", "preprocess", "refstore", "zstd", "filter", "segments", "pack",
            "decode_scan", "decode_write", "fasta_out"]
-K_NAMES_MORE = ["zstd_decode", "parts_unpack", "ranges"]  # the slots from 15 on (K_NAMES stays the 15 slots its users count on); timing_get reports both
+K_NAMES_MORE = ["zstd_decode", "parts_unpack", "ranges", "bgzf"]  # the slots from 15 on (K_NAMES stays the 15 slots its users count on); timing_get reports both
 ZD_OK, ZD_UNSUPPORTED, ZD_MALFORMED = 0, 1, 2
 SEG_RAW, SEG_REF, SEG_DELTA = 0, 1, 2
 PART_STORED, PART_ZSTD = 0, 1
@@ -39,6 +39,7 @@ SYMBOLS = [
     "agc_hip_sample_fasta", "agc_hip_sample_fasta_dev",
     "agc_hip_parts_unpack", "agc_hip_parts_unpack_dev", "agc_hip_sample_fasta_parts", "agc_hip_sample_fasta_parts_dev",
     "agc_hip_ranges_parts", "agc_hip_ranges_parts_dev",
+    "agc_hip_bgzf_bound", "agc_hip_bgzf", "agc_hip_bgzf_dev", "agc_hip_sample_fasta_parts_bgzf", "agc_hip_sample_fasta_parts_bgzf_dev",
     "agc_hip_host_alloc", "agc_hip_host_free",
     "agc_hip_lz_estimate_batch_dev", "agc_hip_lz_estimate_batch",
     "agc_hip_lz_cost_vector_batch_dev", "agc_hip_lz_cost_vector_batch",
@@ -161,6 +162,8 @@ def load():
     fasta_parts = parts_head + [C.c_uint32, u64p, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, u64p, vp, C.c_uint64, u64p]
     L.agc_hip_sample_fasta_parts.argtypes = fasta_parts
     L.agc_hip_sample_fasta_parts_dev.argtypes = fasta_parts
+    L.agc_hip_sample_fasta_parts_bgzf.argtypes = fasta_parts + [u64p, u64p]  # (..., gz, gz_cap, gz_len, text_len, block_off)
+    L.agc_hip_sample_fasta_parts_bgzf_dev.argtypes = fasta_parts + [u64p, u64p]
     ranges_parts = parts_head + [C.c_uint32, u64p, vp, C.c_uint32, C.c_int, vp, C.c_uint64, u64p]
     L.agc_hip_ranges_parts.argtypes = ranges_parts
     L.agc_hip_ranges_parts_dev.argtypes = ranges_parts
@@ -181,6 +184,10 @@ def load():
     L.agc_hip_zstd_decode_batch.argtypes = [vp, C.c_uint32, u8p, u64p, u8p, C.c_uint64, u64p, u32p]
     L.agc_hip_zstd_decode_batch_dev.argtypes = [vp, C.c_uint32, u8p, u64p, vp, C.c_uint64, u64p, u32p]
     L.agc_hip_zstd17_background.argtypes = [vp, C.c_int]
+    L.agc_hip_bgzf_bound.restype = C.c_uint64
+    L.agc_hip_bgzf_bound.argtypes = [C.c_uint64]
+    L.agc_hip_bgzf.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p]
+    L.agc_hip_bgzf_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p]
     L.agc_hip_zstd17_max_input.restype = C.c_uint32
     L.agc_hip_zstd17_resident_frames.argtypes = [vp]
     L.agc_hip_zstd17_resident_frames.restype = C.c_uint32
@@ -222,7 +229,7 @@ def load():
     for s in SYMBOLS:
         f = getattr(L, s)
         if s not in ("agc_hip_destroy", "agc_hip_last_error", "agc_hip_abi_version", "agc_hip_splitters_count", "agc_hip_zstd17_max_input", "agc_hip_zstd17_resident_frames",
-                     "agc_hip_packed_words_bytes", "agc_hip_packed_index_bytes", "agc_hip_group_hash"):
+                     "agc_hip_packed_words_bytes", "agc_hip_packed_index_bytes", "agc_hip_group_hash", "agc_hip_bgzf_bound"):
             f.restype = C.c_int
     _lib = L
     return L
@@ -790,6 +797,50 @@ class Context:
         rc_, n = self.sample_fasta_parts_raw(parts, src, seq_cap, ctg_seg, segs, k, min_match_len, line_length, names, name_off, d_text, text_cap, dev=True)
         self._chk(rc_)
         return n
+
+    def sample_fasta_parts_bgzf_raw(self, parts, src, seq_cap, ctg_seg, segs, k, min_match_len, line_length, names, name_off, gz_ptr, gz_cap, dev=False, block_off=None):
+        """the entry point itself (agc_hip_sample_fasta_parts_bgzf, dev: _dev) -> (return code, stream length -- the bound when the call
+        was refused --, text length); block_off: a uint64 array of ceil(text length / 65280) + 1 entries to fill, or None"""
+        pt, sp, sn, _keep = self._parts_args(parts, src)
+        cs, no = _a(ctg_seg, np.uint64), _a(name_off, np.uint64)
+        sg = np.ascontiguousarray(segs, dtype=SEG_PART_DTYPE)
+        assert cs.size >= 1 and no.size == cs.size and (cs.size == 1 or int(cs[-1]) == sg.size)
+        n, tn = C.c_uint64(0), C.c_uint64(0)
+        fn = self.L.agc_hip_sample_fasta_parts_bgzf_dev if dev else self.L.agc_hip_sample_fasta_parts_bgzf
+        rc_ = fn(self.h, pt.size, pt.ctypes.data, sp, sn, int(seq_cap), cs.size - 1, _p(cs, u64p), sg.ctypes.data, int(k), int(min_match_len), int(line_length),
+                 bytes(names), _p(no, u64p), gz_ptr, int(gz_cap), C.byref(n), C.byref(tn), _p(block_off, u64p))
+        return rc_, n.value, tn.value
+
+    @staticmethod
+    def bgzf_bound(n):
+        """what holds the BGZF stream of any n bytes (agc_hip_bgzf_bound)"""
+        return load().agc_hip_bgzf_bound(int(n))
+
+    def bgzf_raw(self, in_ptr, n, out_ptr, out_cap, dev=False, block_off=None):
+        """the entry point itself (agc_hip_bgzf, dev: _dev; addresses, or None) -> (return code, stream length -- the bound when the call
+        was refused); block_off: a uint64 array of ceil(n / 65280) + 1 entries to fill, or None"""
+        ln = C.c_uint64(0)
+        fn = self.L.agc_hip_bgzf_dev if dev else self.L.agc_hip_bgzf
+        rc_ = fn(self.h, in_ptr, int(n), out_ptr, int(out_cap), C.byref(ln), _p(block_off, u64p))
+        return rc_, ln.value
+
+    def bgzf(self, data, want_offsets=False):
+        """bytes-like -> its BGZF stream as bytes: multi-member gzip (gzip.decompress reads it) in blocks htslib seeks in;
+        want_offsets: -> (stream, the members' offsets: ceil(n / 65280) + 1, the EOF member's last)"""
+        d = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else _a(data, np.uint8)
+        out = np.empty(self.bgzf_bound(d.size), np.uint8)
+        off = np.zeros((d.size + 65279) // 65280 + 1, np.uint64)
+        rc_, ln = self.bgzf_raw(d.ctypes.data if d.size else None, d.size, out.ctypes.data, out.size, block_off=off)
+        self._chk(rc_)
+        return (out[:ln].tobytes(), off) if want_offsets else out[:ln].tobytes()
+
+    def bgzf_dev(self, d_in, n, d_out, out_cap):
+        """n bytes at the device address d_in -> their BGZF stream at the device address d_out (out_cap >= bgzf_bound(n) bytes) ->
+        (stream length, the members' offsets)"""
+        off = np.zeros((int(n) + 65279) // 65280 + 1, np.uint64)
+        rc_, ln = self.bgzf_raw(d_in, n, d_out, out_cap, dev=True, block_off=off)
+        self._chk(rc_)
+        return ln, off
 
     def ranges_parts_raw(self, parts, src, seq_cap, q_seg, wins, min_match_len, letters, out_ptr, out_cap, dev=False):
         """the entry point itself (agc_hip_ranges_parts, dev: _dev) -> (return code, out_off[n_q+1]); wins: SEG_WIN_DTYPE, query q =

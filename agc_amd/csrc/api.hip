@@ -30,6 +30,7 @@
 #include "zstd_decode_kernels.hip"
 #include "parts_unpack_kernels.hip"
 #include "range_kernels.hip"
+#include "bgzf_kernels.hip"
 
 using namespace agc;
 
@@ -167,6 +168,7 @@ struct agc_hip_ctx {
         DevBuf d_zd_src, d_zd_jobs, d_zd_status, d_zd_ws, d_zd_out; // agc_hip_zstd_decode_batch*: the frames, their descriptors, their statuses, the literals workspaces, the bytes
         DevBuf d_pu_dec, d_pu_jobs, d_pu_res, d_pu_wjobs, d_pu_out; // agc_hip_parts_unpack*: the decoded parts, their descriptors, infos + end offsets, the write jobs, the final bytes
         DevBuf d_rg_jobs, d_rg_copy, d_rg_out; // agc_hip_lz_decode_window_batch*, agc_hip_ranges_parts*: the delta window jobs, the RAW / REF window jobs, the symbols
+        DevBuf d_bz_in, d_bz_slots, d_bz_sizes, d_bz_off, d_bz_out; // agc_hip_bgzf*: the input, a slot of 65312 bytes per block, the members' sizes, their offsets, the stream
     } rd;
 
     PackTemp pk1;        // byte-input entry points on the first stream

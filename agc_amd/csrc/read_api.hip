@@ -2,9 +2,10 @@
 // agc_hip_lz_decode_batch (deltas -> symbols), agc_hip_sample_fasta (a sample's plan -> its FASTA text), agc_hip_parts_unpack
 // (archive parts -> packs cut into sequences, references as symbols), agc_hip_sample_fasta_parts (a sample's archive parts -> its
 // FASTA text), agc_hip_lz_decode_window_batch (deltas -> a window of each one's symbols) and agc_hip_ranges_parts (archive parts -> a
-// batch of contig ranges), each with its _dev twin.  The seven are built from the stages below; the sample's host arithmetic is
+// batch of contig ranges), each with its _dev twin, and agc_hip_bgzf (bytes -> a BGZF stream) with agc_hip_sample_fasta_parts_bgzf (a
+// sample's archive parts -> its FASTA text as a BGZF stream).  All are built from the stages below; the sample's host arithmetic is
 // fasta_plan.h, a range's range_plan.h.  Included by api.hip behind the create path (uses its context and helpers; the kernels are
-// lz_decode_kernels.hip, fasta_out_kernels.hip, zstd_decode_kernels.hip, parts_unpack_kernels.hip, range_kernels.hip).
+// lz_decode_kernels.hip, fasta_out_kernels.hip, zstd_decode_kernels.hip, parts_unpack_kernels.hip, range_kernels.hip, bgzf_kernels.hip).
 #include <map>
 
 #include "fasta_plan.h"
@@ -372,6 +373,73 @@ int window_write(agc_hip_ctx *c, const std::vector<WindowJob> &wj, const std::ve
     return AGC_HIP_OK;
 }
 
+// ---- the BGZF stage ----------------------------------------------------------------------------------------------------------------
+// where a BGZF call leaves its stream: the caller's host or device buffer of `cap` bytes, its length, the members' offsets (optional)
+struct GzOut {
+    uint8_t *h_gz, *d_gz;
+    uint64_t cap;
+    uint64_t *h_len, *h_block_off;
+};
+
+// what can be said of a stream of `n` input bytes before anything is launched: the bound into *G.h_len; EINVAL for more blocks than
+// a member count of 32 bits holds, ECAP when the bound does not fit
+int bgzf_capacity(agc_hip_ctx *c, const char *call, uint64_t n, const GzOut &G)
+{
+    *G.h_len = bgzf::bound(n);
+    if (bgzf::block_count(n) > 0xFFFFFFFFull) {
+        c->err = std::string(call) + ": " + std::to_string(n) + " bytes are more than 2^32 - 1 blocks";
+        return AGC_HIP_EINVAL;
+    }
+    return capacity_holds(c, call, "stream", G.cap, bgzf::bound(n));
+}
+
+// The BGZF stage: the n bytes at d_in (capacity checked) -> the stream.  bgzf_block_kernel leaves every block's member in its slot
+// and its size beside it; the sizes come to the host -- the call's one copy down besides the stream itself --, which says where every
+// member begins; bgzf_place_kernel moves them there and appends the EOF member.
+int bgzf_stage(agc_hip_ctx *c, const char *call, const uint8_t *d_in, uint64_t n, const GzOut &G)
+{
+    const uint64_t n_blocks = bgzf::block_count(n);
+    uint8_t *d_out = G.d_gz;
+    CHK(output_buffer(c, d_out, c->rd.d_bz_out, bgzf::bound(n)));
+    CHK(ensure(c, c->rd.d_bz_slots, n_blocks * bgzf::SLOT + 64));
+    CHK(ensure(c, c->rd.d_bz_sizes, n_blocks * sizeof(uint32_t) + 64));
+    CHK(ensure(c, c->rd.d_bz_off, (n_blocks + 1) * sizeof(uint64_t)));
+    std::vector<uint32_t> sizes(n_blocks);
+    std::vector<uint64_t> off(n_blocks + 1);
+    if (n_blocks) {
+        {
+            KTimer t(c, AGC_HIP_K_BGZF);
+            hipLaunchKernelGGL(bgzf_block_kernel, dim3((uint32_t)std::min<uint64_t>(n_blocks, 0x7FFFFFFFull)), dim3(bgzf::THREADS), 0, c->stream, d_in, n, n_blocks,
+                               c->rd.d_bz_slots.as<uint8_t>(), c->rd.d_bz_sizes.as<uint32_t>()); // a workgroup per block
+        }
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(sizes.data(), c->rd.d_bz_sizes.p, n_blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    uint64_t at = 0;
+    for (uint64_t b = 0; b < n_blocks; ++b) {
+        if (sizes[b] < bgzf::HEADER + bgzf::TRAILER || sizes[b] > bgzf::MEMBER_MAX) { // (no address is made of a size no member can have)
+            c->err = std::string(call) + ": block " + std::to_string(b) + " came back with a member of " + std::to_string(sizes[b]) + " bytes";
+            return AGC_HIP_ENODEV;
+        }
+        off[b] = at;
+        at += sizes[b];
+    }
+    off[n_blocks] = at;
+    const uint64_t total = at + bgzf::EOF_BYTES; // (<= the bound: every member is at most its block + 31 bytes)
+    CHK(upload(c, c->rd.d_bz_off.p, off.data(), off.size() * sizeof(uint64_t), c->stream));
+    {
+        KTimer t(c, AGC_HIP_K_BGZF);
+        hipLaunchKernelGGL(bgzf_place_kernel, dim3((uint32_t)std::min<uint64_t>(n_blocks + 1, 0x7FFFFFFFull)), dim3(bgzf::THREADS), 0, c->stream,
+                           (const uint8_t *)c->rd.d_bz_slots.p, (const uint32_t *)c->rd.d_bz_sizes.p, (const uint64_t *)c->rd.d_bz_off.p, n_blocks, d_out);
+    }
+    HIPCHK(c, hipGetLastError());
+    *G.h_len = total;
+    if (G.h_block_off)
+        std::memcpy(G.h_block_off, off.data(), off.size() * sizeof(uint64_t));
+    return hand_back(c, G.h_gz, d_out, total);
+}
+
 const char *delta_refusal(uint32_t status)
 {
     static const char *why[] = {"", "a truncated or malformed token", "'!' at or past the end of the reference", "a match outside the reference",
@@ -634,15 +702,23 @@ static int parts_unpack_impl(agc_hip_ctx *c, uint32_t n, const agc_hip_part *h_p
 // context as it found it; behind the registration only the deltas themselves can still be refused.
 static int sample_fasta_parts_impl(agc_hip_ctx *c, uint32_t n_parts, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap,
                                    uint32_t n_ctg, const uint64_t *h_ctg_seg, const agc_hip_seg_part *h_seg, uint32_t k, uint32_t min_match_len, uint32_t line_length,
-                                   const char *h_names, const uint64_t *h_name_off, uint8_t *h_text, uint8_t *d_text, uint64_t text_cap, uint64_t *h_text_len)
+                                   const char *h_names, const uint64_t *h_name_off, uint8_t *h_text, uint8_t *d_text, uint64_t text_cap, uint64_t *h_text_len,
+                                   const GzOut *gz = nullptr)
 {
+    // gz (agc_hip_sample_fasta_parts_bgzf): the text stays in the context's buffer (h_text, d_text and text_cap are not looked at) and
+    // goes through the BGZF stage from there; the capacity that is checked in step 1 is the stream's
     static const char *call = "sample_fasta_parts";
     if (!c || !h_text_len || (n_ctg && (!h_ctg_seg || !h_name_off || (h_ctg_seg[n_ctg] && !h_seg))) || (n_parts && (!h_parts || (src_bytes && !h_src))) ||
-        (text_cap && !h_text && !d_text))
+        (gz ? !gz->h_len || (gz->cap && !gz->h_gz && !gz->d_gz) : text_cap && !h_text && !d_text))
         return AGC_HIP_EINVAL;
     *h_text_len = 0;
-    if (!n_ctg)
-        return AGC_HIP_OK;
+    if (!n_ctg) {
+        if (!gz)
+            return AGC_HIP_OK;
+        CHK(bgzf_capacity(c, call, 0, *gz));
+        HIPCHK(c, hipSetDevice(c->device));
+        return bgzf_stage(c, call, nullptr, 0, *gz);
+    }
     // 1. the text's size
     uint64_t text = 0;
     if (!fp::plan_text_bytes(n_ctg, h_ctg_seg, k, line_length, h_name_off, [h_seg](uint64_t s) { return h_seg[s].length; }, text)) {
@@ -650,7 +726,11 @@ static int sample_fasta_parts_impl(agc_hip_ctx *c, uint32_t n_parts, const agc_h
         return AGC_HIP_EINVAL;
     }
     *h_text_len = text;
-    CHK(capacity_holds(c, call, "text", text_cap, text));
+    if (gz) {
+        CHK(bgzf_capacity(c, call, text, *gz));
+        h_text = d_text = nullptr;
+    } else
+        CHK(capacity_holds(c, call, "text", text_cap, text));
     TextLaunch T;
     CHK(text_launch(c, d_text, text, T));
     // 2. the plan against the parts and the context
@@ -703,7 +783,24 @@ static int sample_fasta_parts_impl(agc_hip_ctx *c, uint32_t n_parts, const agc_h
     // 5. the new references, registered in one batch from the device buffer
     CHK(register_new_references(c, S, new_ref, min_match_len));
     // 6. agc_hip_sample_fasta's path, the deltas and raw symbols read where the parts stage left them
-    return write_sample(c, Y, c->rd.d_pu_dec.as<uint8_t>(), n_ctg, h_ctg_seg, h_names, h_name_off, line_length, h_text, d_text, T);
+    CHK(write_sample(c, Y, c->rd.d_pu_dec.as<uint8_t>(), n_ctg, h_ctg_seg, h_names, h_name_off, line_length, h_text, d_text, T));
+    // 7. (gz) the text, which write_sample left in the context's buffer, into the stream
+    return gz ? bgzf_stage(c, call, c->rd.d_fa_text.as<uint8_t>(), Y.text, *gz) : AGC_HIP_OK;
+}
+
+// Bytes into a BGZF stream.  The bound follows from n alone, so the capacity is looked at before anything else; then the BGZF stage.
+static int bgzf_impl(agc_hip_ctx *c, const uint8_t *h_in, const uint8_t *d_in, uint64_t n, const GzOut &G)
+{
+    if (!c || !G.h_len || (n && !h_in && !d_in) || (G.cap && !G.h_gz && !G.d_gz))
+        return AGC_HIP_EINVAL;
+    CHK(bgzf_capacity(c, "bgzf", n, G));
+    HIPCHK(c, hipSetDevice(c->device));
+    if (h_in && n) {
+        CHK(ensure(c, c->rd.d_bz_in, n + 64));
+        CHK(upload(c, c->rd.d_bz_in.p, h_in, n, c->stream));
+        d_in = c->rd.d_bz_in.as<uint8_t>();
+    }
+    return bgzf_stage(c, "bgzf", d_in, n, G);
 }
 
 // The windowed LZ decode: the output's layout follows from the windows' sizes, so the capacity is looked at first; the scan stage
@@ -882,6 +979,37 @@ static int ranges_parts_impl(agc_hip_ctx *c, uint32_t n_parts, const agc_hip_par
 }
 
 extern "C" {
+
+uint64_t agc_hip_bgzf_bound(uint64_t n_bytes) { return bgzf::bound(n_bytes); }
+
+int agc_hip_bgzf(agc_hip_ctx *c, const uint8_t *h_in, uint64_t n, uint8_t *h_out, uint64_t out_cap, uint64_t *h_out_len, uint64_t *h_block_off)
+{
+    return bgzf_impl(c, h_in, nullptr, n, {h_out, nullptr, out_cap, h_out_len, h_block_off});
+}
+
+int agc_hip_bgzf_dev(agc_hip_ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_len, uint64_t *h_block_off)
+{
+    return bgzf_impl(c, nullptr, d_in, n, {nullptr, d_out, out_cap, h_out_len, h_block_off});
+}
+
+int agc_hip_sample_fasta_parts_bgzf(agc_hip_ctx *c, uint32_t n_parts, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap, uint32_t n_ctg,
+                                    const uint64_t *h_ctg_seg, const agc_hip_seg_part *h_seg, uint32_t k, uint32_t min_match_len, uint32_t line_length, const char *h_names,
+                                    const uint64_t *h_name_off, uint8_t *h_gz, uint64_t gz_cap, uint64_t *h_gz_len, uint64_t *h_text_len, uint64_t *h_block_off)
+{
+    const GzOut G = {h_gz, nullptr, gz_cap, h_gz_len, h_block_off};
+    return sample_fasta_parts_impl(c, n_parts, h_parts, h_src, src_bytes, seq_cap, n_ctg, h_ctg_seg, h_seg, k, min_match_len, line_length, h_names, h_name_off, nullptr, nullptr,
+                                   0, h_text_len, &G);
+}
+
+int agc_hip_sample_fasta_parts_bgzf_dev(agc_hip_ctx *c, uint32_t n_parts, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap,
+                                        uint32_t n_ctg, const uint64_t *h_ctg_seg, const agc_hip_seg_part *h_seg, uint32_t k, uint32_t min_match_len, uint32_t line_length,
+                                        const char *h_names, const uint64_t *h_name_off, uint8_t *d_gz, uint64_t gz_cap, uint64_t *h_gz_len, uint64_t *h_text_len,
+                                        uint64_t *h_block_off)
+{
+    const GzOut G = {nullptr, d_gz, gz_cap, h_gz_len, h_block_off};
+    return sample_fasta_parts_impl(c, n_parts, h_parts, h_src, src_bytes, seq_cap, n_ctg, h_ctg_seg, h_seg, k, min_match_len, line_length, h_names, h_name_off, nullptr, nullptr,
+                                   0, h_text_len, &G);
+}
 
 int agc_hip_lz_decode_window_batch(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const uint8_t *h_enc, const uint64_t *h_enc_off, const uint8_t *h_rc,
                                    const uint32_t *h_win_from, const uint32_t *h_win_len, uint8_t *h_out, uint64_t out_cap, uint64_t *h_out_off)

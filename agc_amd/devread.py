@@ -8,6 +8,9 @@ sample_fasta_parts / sample_fasta_parts_dev: the host reader only reads the coll
 sample needs (GetSampleParts); their bytes go to the device as the archive holds them and are zstd-decoded, cut into sequences,
 un-tupled and -- the references not registered yet -- registered there (agc_hip_sample_fasta_parts).
 
+sample_fasta_bgzf / sample_fasta_bgzf_dev: the parts path with the text compressed where it is made -- BGZF, block deflate with
+dynamic Huffman codes (agc_hip_sample_fasta_parts_bgzf) -- so that a third of the bytes cross to the host.
+
 ranges / ranges_dev: a batch of windows (sample, contig, start, end) -- the range as GetCtgSeq reads it: inclusive, -1 / -1 the whole
 contig -- through the same parts path: the host reader says which segments each range touches, which window of each, and which
 stored parts the whole batch needs (GetRangeParts); the device decodes those parts and writes every window straight to its place
@@ -18,6 +21,7 @@ stored parts the whole batch needs (GetRangeParts); the device decodes those par
     text = r.sample_fasta("HG00438.1")          # bytes, what `agc getset` writes
     d = r.sample_fasta_dev("HG00438.1")         # the same as a torch uint8 tensor on the device
     text = r.sample_fasta_parts("HG00438.1")    # the same bytes, nothing but metadata decoded on the host
+    gz = r.sample_fasta_bgzf("HG00438.1")       # the same text as a BGZF stream (gzip.decompress(gz) == text), compressed on the device
     seqs = r.ranges([("HG00438.1", "chr1", 1000, 1999), (None, "chrM", -1, -1)])   # a list of bytes: letters, one per query
     d, off = r.ranges_dev(queries, letters=False)                                  # symbol codes on the device, query q = d[off[q]:off[q+1]]
     r.close()
@@ -144,6 +148,31 @@ class DeviceReader:
             rc, _n = self.ctx.sample_fasta_parts_raw(*args, line_length, names, name_off, out.data_ptr(), need, dev=True)
             self._after(rc, new)
         return out
+
+    def sample_fasta_bgzf(self, name, line_length=80):
+        """-> bytes: sample_fasta_parts's text as a BGZF stream (agc_hip_sample_fasta_parts_bgzf) -- multi-member gzip in blocks of 65280
+        bytes that gzip.decompress reads and htslib seeks in; the text itself never leaves the device"""
+        args, (names, name_off), new = self.parts(name)
+        rc, need, _text = self.ctx.sample_fasta_parts_bgzf_raw(*args, line_length, names, name_off, self._pinned, self._pinned_cap)
+        if rc == capi.ECAP:  # (the bound follows from the segments' lengths: nothing was launched or registered)
+            rc, need, _text = self.ctx.sample_fasta_parts_bgzf_raw(*args, line_length, names, name_off, self._pinned_buffer(need), self._pinned_cap)
+        self._after(rc, new)
+        return C.string_at(self._pinned, need)
+
+    def sample_fasta_bgzf_dev(self, name, line_length=80):
+        """-> (the same stream as a torch uint8 tensor on the context's device, the members' offsets in it: numpy uint64, one per block
+        of 65280 text bytes and the EOF member's last)"""
+        import torch
+        args, (names, name_off), new = self.parts(name)
+        rc, need, text = self.ctx.sample_fasta_parts_bgzf_raw(*args, line_length, names, name_off, None, 0, dev=True)
+        if rc != capi.ECAP:  # (a stream has 28 bytes at least: anything else is a refusal)
+            self._after(rc, new)
+        out = torch.empty(need, dtype=torch.uint8, device="cuda")
+        off = np.zeros((text + 65279) // 65280 + 1, np.uint64)
+        torch.cuda.synchronize()
+        rc, n, _text = self.ctx.sample_fasta_parts_bgzf_raw(*args, line_length, names, name_off, out.data_ptr(), need, dev=True, block_off=off)
+        self._after(rc, new)
+        return out[:n], off
 
     def range_parts(self, queries):
         """the batch's windows and stored parts (reader.CAGCFile.GetRangeParts, without the references registered already) -> (the

@@ -66,7 +66,8 @@ enum {
     AGC_HIP_K_ZSTD_DECODE = 15,  /* agc_hip_zstd_decode_batch*: zstd_decode_kernel (zstd_decode_kernels.hip) */
     AGC_HIP_K_PARTS_UNPACK = 16, /* agc_hip_parts_unpack*, agc_hip_sample_fasta_parts*: pack_index_kernel, tuples_size_kernel, tuples_unpack_kernel (parts_unpack_kernels.hip) */
     AGC_HIP_K_RANGES = 17,       /* agc_hip_lz_decode_window_batch*, agc_hip_ranges_parts*: lz_decode_window_kernel, segment_window_kernel, letters_kernel (range_kernels.hip) */
-    AGC_HIP_K_COUNT = 18
+    AGC_HIP_K_BGZF = 18,         /* agc_hip_bgzf*, agc_hip_sample_fasta_parts_bgzf*: bgzf_block_kernel, bgzf_place_kernel (bgzf_kernels.hip) */
+    AGC_HIP_K_COUNT = 19
 };
 int agc_hip_timing_enable(agc_hip_ctx *ctx, int on);
 int agc_hip_timing_reset(agc_hip_ctx *ctx);
@@ -611,6 +612,38 @@ int agc_hip_sample_fasta_parts_dev(agc_hip_ctx *ctx, uint32_t n_parts, const agc
                                    uint32_t n_ctg, const uint64_t *h_ctg_seg, const agc_hip_seg_part *h_seg, uint32_t k, uint32_t min_match_len,
                                    uint32_t line_length, const char *h_names, const uint64_t *h_name_off, uint8_t *d_text, uint64_t text_cap,
                                    uint64_t *h_text_len);
+
+/* Bytes into BGZF -- the blocked gzip of the SAM specification (4.1), what `bgzip` writes: plain multi-member gzip that htslib seeks
+ * in.  The input is cut into blocks of 65280 bytes; every block becomes one gzip member with the fixed 18-byte header (MTIME 0, XFL 0,
+ * OS ff, the BC subfield), a deflate payload of ONE block -- dynamic Huffman codes over literals and end-of-block, no match search, or
+ * a stored block whenever that is not larger --, CRC-32 and ISIZE; the 28-byte EOF member ends the stream.  The stream is reproducible:
+ * the same input gives the same bytes, and they are the bytes the CPU build of agc_amd/csrc/bgzf.h writes.
+ *
+ * agc_hip_bgzf_bound(n) = n + 31 * ceil(n / 65280) + 28 holds the stream of any n bytes; every capacity check uses it, never a size
+ * that depends on the data.  *h_out_len always receives a size: the bound when the call is refused for its capacity, the stream's
+ * length after AGC_HIP_OK.  h_block_off (optional): ceil(n / 65280) + 1 offsets, where each member -- the EOF member last -- begins in
+ * the stream.  AGC_HIP_ECAP: out_cap is smaller than the bound; nothing was launched or written.  AGC_HIP_EINVAL: a NULL that is
+ * needed, more than 2^32 - 1 blocks.  n == 0: AGC_HIP_OK and the 28 bytes of the EOF member.  d_in / d_out (_dev): device memory at
+ * any alignment (16-byte loads when d_in is 16-byte aligned, byte loads otherwise); no byte of d_out outside the stream is written.
+ * One copy of 4 bytes per block comes to the host per call: the members' sizes, from which it says where each one goes. */
+uint64_t agc_hip_bgzf_bound(uint64_t n_bytes);
+int agc_hip_bgzf(agc_hip_ctx *ctx, const uint8_t *h_in, uint64_t n, uint8_t *h_out, uint64_t out_cap, uint64_t *h_out_len, uint64_t *h_block_off);
+int agc_hip_bgzf_dev(agc_hip_ctx *ctx, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_len, uint64_t *h_block_off);
+
+/* agc_hip_sample_fasta_parts with the text compressed where it is made: the arguments and the order of events of that call, the text
+ * written to a buffer the context owns and from there into the BGZF stream of agc_hip_bgzf.  *h_text_len = the text's size (step 1),
+ * *h_gz_len = agc_hip_bgzf_bound(text size) until the stream is written, then its length; h_block_off (optional):
+ * ceil(text size / 65280) + 1 offsets.  AGC_HIP_ECAP: gz_cap is smaller than that bound -- before any launch and before any
+ * registration.  Everything agc_hip_sample_fasta_parts refuses is refused the same way and leaves the same state.  A plan without a
+ * contig gives the EOF member alone.  The host variant copies the stream's bytes, not the bound, to h_gz. */
+int agc_hip_sample_fasta_parts_bgzf(agc_hip_ctx *ctx, uint32_t n_parts, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap,
+                                    uint32_t n_ctg, const uint64_t *h_ctg_seg, const agc_hip_seg_part *h_seg, uint32_t k, uint32_t min_match_len,
+                                    uint32_t line_length, const char *h_names, const uint64_t *h_name_off, uint8_t *h_gz, uint64_t gz_cap, uint64_t *h_gz_len,
+                                    uint64_t *h_text_len, uint64_t *h_block_off);
+int agc_hip_sample_fasta_parts_bgzf_dev(agc_hip_ctx *ctx, uint32_t n_parts, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap,
+                                        uint32_t n_ctg, const uint64_t *h_ctg_seg, const agc_hip_seg_part *h_seg, uint32_t k, uint32_t min_match_len,
+                                        uint32_t line_length, const char *h_names, const uint64_t *h_name_off, uint8_t *d_gz, uint64_t gz_cap, uint64_t *h_gz_len,
+                                        uint64_t *h_text_len, uint64_t *h_block_off);
 
 /* One window of a batch of contig ranges: the segment as agc_hip_seg_part names it, and the symbols [win_from, win_from + win_len)
  * of its ORIENTED form (win_len >= 1, win_from + win_len <= length).  The k-symbol overlap between segments is the caller's to
