@@ -528,6 +528,19 @@ bool CAGCFile::GetSampleCodes(const std::string &sample, std::vector<std::string
     return true;
 }
 
+// get_segment's three cases as the plans name them: the segment's kind, and -- RAW, DELTA -- where its bytes lie: sequence `index` of
+// pack `pack_no` of its group's stream
+struct SegWhere {
+    uint32_t kind, pack_no, index;
+};
+static SegWhere seg_where(const SegDesc &s, uint32_t pack_cardinality)
+{
+    const bool raw = s.group_id < NO_RAW_GROUPS;
+    const uint32_t kind = raw ? SamplePlan::RAW : s.in_group_id == 0 ? SamplePlan::REF : SamplePlan::DELTA;
+    const uint32_t i = kind == SamplePlan::REF ? 0 : raw ? s.in_group_id : s.in_group_id - 1;
+    return {kind, i / pack_cardinality, i % pack_cardinality};
+}
+
 // The sources of decode_contig's segments instead of the segments: get_segment's three cases without its decode
 bool CAGCFile::GetSamplePlan(const std::string &sample, SamplePlan &P) const
 {
@@ -545,8 +558,10 @@ bool CAGCFile::GetSamplePlan(const std::string &sample, SamplePlan &P) const
         P.names.insert(P.names.end(), c.name.begin(), c.name.end());
         P.name_off.push_back(P.names.size());
         for (const SegDesc &s : c.segs) {
-            const bool raw = s.group_id < NO_RAW_GROUPS;
-            uint32_t kind = raw ? SamplePlan::RAW : s.in_group_id == 0 ? SamplePlan::REF : SamplePlan::DELTA, length = s.raw_length;
+            const SegWhere w = seg_where(s, p->pack);
+            const uint32_t kind = w.kind;
+            const bool raw = kind == SamplePlan::RAW;
+            uint32_t length = s.raw_length;
             uint64_t off = 0;
             size_t n = 0;
             if (kind == SamplePlan::REF) {
@@ -555,10 +570,9 @@ bool CAGCFile::GetSamplePlan(const std::string &sample, SamplePlan &P) const
                     return false;
                 length = (uint32_t)ref->size();
             } else {
-                const uint32_t idx = raw ? s.in_group_id : s.in_group_id - 1;
                 const bytes_t *pk;
                 const uint8_t *b;
-                if (!p->get_pack(s.group_id, idx / p->pack, pk) || !nth_in_pack(*pk, idx % p->pack, b, n) || n > 0xFFFFFFFFull)
+                if (!p->get_pack(s.group_id, w.pack_no, pk) || !nth_in_pack(*pk, w.index, b, n) || n > 0xFFFFFFFFull)
                     return false;
                 off = P.bytes.size();
                 P.bytes.insert(P.bytes.end(), b, b + n);
@@ -594,7 +608,7 @@ bool CAGCFile::GetSamplePlan(const std::string &sample, SamplePlan &P) const
 // then the packs of `packs` ((group, pack number) -> its place among the parts, filled here), and every RAW / DELTA segment's part.
 // false: a part the archive does not hold
 template <class P_t>
-static bool list_parts(const Archive &ar, uint32_t pack_cardinality, const std::map<uint32_t, uint32_t> &refs, std::map<std::pair<uint32_t, uint32_t>, uint32_t> &packs, P_t &P)
+static bool list_parts(const Archive &ar, const std::map<uint32_t, uint32_t> &refs, std::map<std::pair<uint32_t, uint32_t>, uint32_t> &packs, P_t &P)
 {
     auto add = [&](const std::string &stream, uint32_t no, uint32_t group, bool ref) {
         const uint8_t *ptr;
@@ -620,11 +634,29 @@ static bool list_parts(const Archive &ar, uint32_t pack_cardinality, const std::
             return false;
     }
     for (size_t s = 0; s < P.kind.size(); ++s)
-        if (P.kind[s] != SamplePlan::REF) {
-            const uint32_t i = P.kind[s] == SamplePlan::RAW ? P.in_group_id[s] : P.in_group_id[s] - 1;
-            P.part[s] = packs[std::make_pair(P.group_id[s], i / pack_cardinality)];
-        }
+        if (P.kind[s] != SamplePlan::REF)
+            P.part[s] = packs[std::make_pair(P.group_id[s], P.part[s])]; // (add_segment left the pack's number there)
     return true;
+}
+
+// One segment into SampleParts / RangeParts (P: either): its common columns, the pack it lies in into `packs`, and its group into
+// `refs` when the caller does not have that group's reference (have: sorted)
+template <class P_t>
+static void add_segment(const SegDesc &s, uint32_t pack_cardinality, const std::vector<uint32_t> &have, std::map<uint32_t, uint32_t> &refs,
+                        std::map<std::pair<uint32_t, uint32_t>, uint32_t> &packs, P_t &P)
+{
+    const SegWhere w = seg_where(s, pack_cardinality);
+    if (w.kind != SamplePlan::REF)
+        packs.emplace(std::make_pair(s.group_id, w.pack_no), 0);
+    if (w.kind != SamplePlan::RAW && !std::binary_search(have.begin(), have.end(), s.group_id))
+        refs.emplace(s.group_id, 0);
+    P.group_id.push_back(s.group_id);
+    P.in_group_id.push_back(s.in_group_id);
+    P.rc.push_back(s.rc ? 1 : 0);
+    P.length.push_back(s.raw_length);
+    P.kind.push_back(w.kind);
+    P.part.push_back(w.pack_no); // (list_parts turns the pack's number into its place among the parts)
+    P.index.push_back(w.index);
 }
 
 // GetSamplePlan without its decode: which parts decode_ref_part / decode_pack_part would be handed, and how they would read them
@@ -648,28 +680,11 @@ bool CAGCFile::GetSampleParts(const std::string &sample, const uint32_t *have_gr
     for (const CtgDesc &c : sd.ctgs) {
         P.names.insert(P.names.end(), c.name.begin(), c.name.end());
         P.name_off.push_back(P.names.size());
-        for (const SegDesc &s : c.segs) {
-            const bool raw = s.group_id < NO_RAW_GROUPS;
-            const uint32_t kind = raw ? SamplePlan::RAW : s.in_group_id == 0 ? SamplePlan::REF : SamplePlan::DELTA;
-            uint32_t idx = 0;
-            if (kind != SamplePlan::REF) {
-                const uint32_t i = raw ? s.in_group_id : s.in_group_id - 1;
-                packs.emplace(std::make_pair(s.group_id, i / p->pack), 0);
-                idx = i % p->pack;
-            }
-            if (!raw && !std::binary_search(have.begin(), have.end(), s.group_id))
-                refs.emplace(s.group_id, 0);
-            P.group_id.push_back(s.group_id);
-            P.in_group_id.push_back(s.in_group_id);
-            P.rc.push_back(s.rc ? 1 : 0);
-            P.length.push_back(s.raw_length);
-            P.kind.push_back(kind);
-            P.part.push_back(0); // (filled below, when the packs have their places)
-            P.index.push_back(idx);
-        }
+        for (const SegDesc &s : c.segs)
+            add_segment(s, p->pack, have, refs, packs, P);
         P.ctg_seg.push_back(P.kind.size());
     }
-    return list_parts(p->ar, p->pack, refs, packs, P);
+    return list_parts(p->ar, refs, packs, P);
 }
 
 // The same for a batch of contig ranges: every query's contig is looked up as GetCtgSeq does, its windows are range_plan.h's, and the
@@ -698,31 +713,14 @@ bool CAGCFile::GetRangeParts(const std::vector<RangeQuery> &queries, const uint3
         const std::vector<SegDesc> &segs = p->samples[sid].ctgs[cid].segs;
         const uint64_t n = rp::contig_windows(
             segs.size(), [&](uint64_t s) { return segs[s].raw_length; }, p->k, queries[q].from, queries[q].to, [&](uint64_t si, uint32_t win_from, uint32_t win_len) {
-                const SegDesc &s = segs[si];
-                const bool raw = s.group_id < NO_RAW_GROUPS;
-                const uint32_t kind = raw ? SamplePlan::RAW : s.in_group_id == 0 ? SamplePlan::REF : SamplePlan::DELTA;
-                uint32_t idx = 0;
-                if (kind != SamplePlan::REF) {
-                    const uint32_t i = raw ? s.in_group_id : s.in_group_id - 1;
-                    packs.emplace(std::make_pair(s.group_id, i / p->pack), 0);
-                    idx = i % p->pack;
-                }
-                if (!raw && !std::binary_search(have.begin(), have.end(), s.group_id))
-                    refs.emplace(s.group_id, 0);
-                P.group_id.push_back(s.group_id);
-                P.in_group_id.push_back(s.in_group_id);
-                P.rc.push_back(s.rc ? 1 : 0);
-                P.length.push_back(s.raw_length);
-                P.kind.push_back(kind);
-                P.part.push_back(0); // (filled by list_parts)
-                P.index.push_back(idx);
+                add_segment(segs[si], p->pack, have, refs, packs, P);
                 P.win_from.push_back(win_from);
                 P.win_len.push_back(win_len);
             });
         P.q_len.push_back(n);
         P.q_seg.push_back(P.kind.size());
     }
-    return list_parts(p->ar, p->pack, refs, packs, P);
+    return list_parts(p->ar, refs, packs, P);
 }
 
 bool CAGCFile::GetSampleFasta(const std::string &sample, std::string &out, uint32_t line_length) const

@@ -3,8 +3,10 @@
 // (archive parts -> packs cut into sequences, references as symbols), agc_hip_sample_fasta_parts (a sample's archive parts -> its
 // FASTA text), agc_hip_lz_decode_window_batch (deltas -> a window of each one's symbols) and agc_hip_ranges_parts (archive parts -> a
 // batch of contig ranges), each with its _dev twin, and agc_hip_bgzf (bytes -> a BGZF stream) with agc_hip_sample_fasta_parts_bgzf (a
-// sample's archive parts -> its FASTA text as a BGZF stream).  All are built from the stages below; the sample's host arithmetic is
-// fasta_plan.h, a range's range_plan.h.  Included by api.hip behind the create path (uses its context and helpers; the kernels are
+// sample's archive parts -> its FASTA text as a BGZF stream).  All are built from the stages below.  The host arithmetic is not here:
+// layout, jobs and first complaint of a sample are fasta_plan.h's, of a range batch range_plan.h's (both run on the CPU in tests/);
+// this file checks arguments, uploads, launches and copies back.  The two calls from archive parts share PartsCall, the two LZ
+// decode calls scan_delta_batch.  Included by api.hip behind the create path (uses its context and helpers; the kernels are
 // lz_decode_kernels.hip, fasta_out_kernels.hip, zstd_decode_kernels.hip, parts_unpack_kernels.hip, range_kernels.hip, bgzf_kernels.hip).
 #include <map>
 
@@ -14,23 +16,44 @@
 namespace {
 
 // ---- checks: the message begins with the call's name ----------------------------------------------------------------------------
+int refuse(agc_hip_ctx *c, const std::string &what, int code = AGC_HIP_EINVAL)
+{
+    c->err = what;
+    return code;
+}
+
 // item i of a batch (a "delta", a "frame") lies at [off[i], off[i + 1])
 int offsets_ascend(agc_hip_ctx *c, const char *call, const char *item, const uint64_t *off, uint32_t i)
 {
-    if (off[i + 1] >= off[i])
-        return AGC_HIP_OK;
-    c->err = std::string(call) + ": " + item + " " + std::to_string(i) + " ends in front of its start";
-    return AGC_HIP_EINVAL;
+    return off[i + 1] >= off[i] ? AGC_HIP_OK : refuse(c, std::string(call) + ": " + item + " " + std::to_string(i) + " ends in front of its start");
 }
 
 // the caller's buffer (the "output" buffer, the "text" buffer) has room for what the call is about to write
 int capacity_holds(agc_hip_ctx *c, const char *call, const char *buffer, uint64_t cap, uint64_t need)
 {
-    if (need <= cap)
-        return AGC_HIP_OK;
-    c->err = std::string(call) + ": the " + buffer + " buffer holds " + std::to_string(cap) + " bytes, " + std::to_string(need) + " are needed";
-    return AGC_HIP_ECAP;
+    return need <= cap ? AGC_HIP_OK : refuse(c, std::string(call) + ": the " + buffer + " buffer holds " + std::to_string(cap) + " bytes, " + std::to_string(need) + " are needed", AGC_HIP_ECAP);
 }
+
+// the group has a registered reference; the symbols of it, -1: it has none
+bool registered(const agc_hip_ctx *c, uint32_t gid) { return gid < c->refs.size() && c->refs[gid].valid; }
+int64_t registered_size(const agc_hip_ctx *c, uint32_t gid) { return registered(c, gid) ? (int64_t)c->refs[gid].ref_size : (int64_t)-1; }
+
+// A launch that gives every 16-byte chunk of what it writes a lane, 256 to a block.  add(): `bytes` bytes at address p join it (a: that
+// address's alignment) -> the piece's first chunk.  A launch of one piece is {a, n_chunks, blocks} after one add().
+struct ChunkLaunch {
+    uint32_t a = 0; // of the piece added LAST: a launch of several pieces copies it after every add()
+    uint64_t n_chunks = 0, blocks = 0;
+    uint64_t add(const void *p, uint64_t bytes)
+    {
+        const uint64_t first = n_chunks;
+        a = (uint32_t)((uintptr_t)p & (fo::CHUNK - 1));
+        n_chunks += fo::chunk_count(a, bytes);
+        blocks = (n_chunks + 255) / 256;
+        return first;
+    }
+    // `what` ("sample_fasta: a text of 5 bytes is") more than one launch `does`
+    int fits(agc_hip_ctx *c, const std::string &what, const char *does) const { return blocks <= 0x7FFFFFFFull ? AGC_HIP_OK : refuse(c, what + " more than one launch " + does); }
+};
 
 // ---- stages -------------------------------------------------------------------------------------------------------------------------
 // where a call writes: the caller's device buffer, or -- d_out == nullptr -- the context's, grown to hold `bytes`
@@ -85,22 +108,26 @@ int decode_write(agc_hip_ctx *c, uint32_t n, const uint8_t *d_enc, uint8_t *d_ou
     return AGC_HIP_OK;
 }
 
-// how fasta_text_kernel is launched for a text of `text` bytes at d_text (nullptr: the context's buffer, which is aligned)
-struct TextLaunch {
-    uint32_t a;
-    uint64_t n_chunks, blocks;
-};
-
-int text_launch(agc_hip_ctx *c, const uint8_t *d_text, uint64_t text, TextLaunch &T)
+// The scan stage with its verdict on deltas whose lengths a plan declares (job i: out_len, and the segment or window -- `noun` --
+// item[i] it belongs to): every one well formed and of that length, or the first that is not is named.  No job: no launch.
+int scan_declared_lengths(agc_hip_ctx *c, const char *call, const char *noun, const std::vector<DecodeJob> &jobs, const std::vector<uint32_t> &item, const uint8_t *d_bytes)
 {
-    T.a = d_text ? (uint32_t)((uintptr_t)d_text & (fo::CHUNK - 1)) : 0;
-    T.n_chunks = fo::chunk_count(T.a, text);
-    T.blocks = (T.n_chunks + 255) / 256;
-    if (T.blocks > 0x7FFFFFFFull) {
-        c->err = "sample_fasta: a text of " + std::to_string(text) + " bytes is more than one launch writes";
-        return AGC_HIP_EINVAL;
-    }
+    if (jobs.empty())
+        return AGC_HIP_OK;
+    std::vector<DecodeResult> res;
+    CHK(decode_scan(c, jobs, d_bytes, res));
+    for (size_t i = 0; i < jobs.size(); ++i)
+        if (res[i].status != lzd::OK || res[i].len != jobs[i].out_len)
+            return refuse(c, std::string(call) + ": " + noun + " " + std::to_string(item[i]) +
+                                 (res[i].status != lzd::OK ? " has a malformed delta" : " has a delta that decodes to " + std::to_string(res[i].len) + " symbols, its length says " + std::to_string(jobs[i].out_len)));
     return AGC_HIP_OK;
+}
+
+// how fasta_text_kernel is launched for a text of `text` bytes at d_text (nullptr: the context's buffer, which is aligned)
+int text_launch(agc_hip_ctx *c, const uint8_t *d_text, uint64_t text, ChunkLaunch &T)
+{
+    T.add(d_text, text);
+    return T.fits(c, "sample_fasta: a text of " + std::to_string(text) + " bytes is", "writes");
 }
 
 using SampleLayout = fp::SampleLayout<DecodeJob, CopyJob>;
@@ -109,20 +136,11 @@ using SampleLayout = fp::SampleLayout<DecodeJob, CopyJob>;
 // the scan stage, against the length the plan declares, before anything is written: the write stage and segment_copy_kernel then lay
 // the segments out in the symbol buffer, fasta_text_kernel writes the text.
 int write_sample(agc_hip_ctx *c, const SampleLayout &Y, const uint8_t *d_bytes, uint32_t n_ctg, const uint64_t *h_ctg_seg, const char *h_names,
-                 const uint64_t *h_name_off, uint32_t line_length, uint8_t *h_text, uint8_t *d_text, const TextLaunch &T)
+                 const uint64_t *h_name_off, uint32_t line_length, uint8_t *h_text, uint8_t *d_text, const ChunkLaunch &T)
 {
     CHK(upload_refs(c));
     const uint32_t n_dj = (uint32_t)Y.dj.size(), n_cj = (uint32_t)Y.cj.size();
-    if (n_dj) {
-        std::vector<DecodeResult> res;
-        CHK(decode_scan(c, Y.dj, d_bytes, res));
-        for (uint32_t i = 0; i < n_dj; ++i)
-            if (res[i].status != lzd::OK || res[i].len != Y.dj[i].out_len) {
-                c->err = "sample_fasta: segment " + std::to_string(Y.dj_seg[i]) +
-                         (res[i].status != lzd::OK ? " has a malformed delta" : " decodes to " + std::to_string(res[i].len) + " symbols, its length says " + std::to_string(Y.dj[i].out_len));
-                return AGC_HIP_EINVAL;
-            }
-    }
+    CHK(scan_declared_lengths(c, "sample_fasta", "segment", Y.dj, Y.dj_seg, d_bytes));
     // every segment has passed: from here on things are written
     CHK(ensure(c, c->rd.d_fa_sym, Y.sym_total + 64));
     uint8_t *d_sym = c->rd.d_fa_sym.as<uint8_t>();
@@ -191,13 +209,19 @@ struct PartsState {
     uint64_t dec_bytes = 0;
 
     uint32_t status(uint32_t i) const { return info[i].status; }
-    // sequence q < min(count, seq_cap) of pack i, as bytes of d_pu_dec
-    void sequence(uint32_t i, uint32_t q, uint64_t &off, uint32_t &n) const
+    // sequence q of pack i, as bytes [off, off + n) of d_pu_dec; false: q is at or above the pack's count or seq_cap, `why` says so
+    bool locate(uint32_t i, uint32_t q, uint64_t &off, uint32_t &n, std::string &why) const
     {
+        if (q >= info[i].count || q >= seq_cap) {
+            why = "sequence " + std::to_string(q) + " of part " + std::to_string(i) + ", which has " + std::to_string(info[i].count) + " (at most " + std::to_string(seq_cap) +
+                  " are indexed)";
+            return false;
+        }
         const uint32_t *row = seq_end.data() + (size_t)jobs[i].seq_row * seq_cap;
         const uint32_t begin = q ? row[q - 1] + 1 : 0;
         off = jobs[i].dec_off + begin;
         n = row[q] - begin;
+        return true;
     }
 };
 
@@ -210,10 +234,8 @@ int parts_check(agc_hip_ctx *c, const char *call, uint32_t n, const agc_hip_part
                           : p.coding > AGC_HIP_PART_ZSTD                    ? "has an unknown coding"
                           : p.content > AGC_HIP_PART_REF_TUPLES             ? "has an unknown content"
                                                                             : nullptr;
-        if (why) {
-            c->err = std::string(call) + ": part " + std::to_string(i) + " " + why;
-            return AGC_HIP_EINVAL;
-        }
+        if (why)
+            return refuse(c, std::string(call) + ": part " + std::to_string(i) + " " + why);
     }
     return AGC_HIP_OK;
 }
@@ -317,22 +339,17 @@ int unpack_write(agc_hip_ctx *c, std::vector<UnpackJob> &jobs, uint8_t *d_out)
 {
     if (jobs.empty())
         return AGC_HIP_OK;
-    uint64_t n_chunks = 0;
+    ChunkLaunch L;
     for (UnpackJob &j : jobs) {
-        j.a = (uint32_t)((uintptr_t)(d_out + j.out_off) & (fo::CHUNK - 1));
-        j.first_chunk = n_chunks;
-        n_chunks += fo::chunk_count(j.a, j.n);
+        j.first_chunk = L.add(d_out + j.out_off, j.n);
+        j.a = L.a;
     }
-    const uint64_t blocks = (n_chunks + 255) / 256;
-    if (blocks > 0x7FFFFFFFull) {
-        c->err = "parts_unpack: " + std::to_string(n_chunks) + " chunks of 16 bytes are more than one launch writes";
-        return AGC_HIP_EINVAL;
-    }
+    CHK(L.fits(c, "parts_unpack: " + std::to_string(L.n_chunks) + " chunks of 16 bytes are", "writes"));
     CHK(ensure(c, c->rd.d_pu_wjobs, jobs.size() * sizeof(UnpackJob)));
     CHK(upload(c, c->rd.d_pu_wjobs.p, jobs.data(), jobs.size() * sizeof(UnpackJob), c->stream));
     {
         KTimer t(c, AGC_HIP_K_PARTS_UNPACK);
-        hipLaunchKernelGGL(tuples_unpack_kernel, dim3((uint32_t)blocks), dim3(256), 0, c->stream, (const UnpackJob *)c->rd.d_pu_wjobs.p, (uint32_t)jobs.size(), n_chunks,
+        hipLaunchKernelGGL(tuples_unpack_kernel, dim3((uint32_t)L.blocks), dim3(256), 0, c->stream, (const UnpackJob *)c->rd.d_pu_wjobs.p, (uint32_t)jobs.size(), L.n_chunks,
                            (const uint8_t *)c->rd.d_pu_dec.p, d_out);
     }
     HIPCHK(c, hipGetLastError());
@@ -345,12 +362,9 @@ int unpack_write(agc_hip_ctx *c, std::vector<UnpackJob> &jobs, uint8_t *d_out)
 int window_write(agc_hip_ctx *c, const std::vector<WindowJob> &wj, const std::vector<WindowCopyJob> &cj, const uint8_t *d_enc, uint8_t *d_out, uint64_t total, bool letters)
 {
     const uint32_t n_wj = (uint32_t)wj.size(), n_cj = (uint32_t)cj.size();
-    const uint32_t a = (uint32_t)((uintptr_t)d_out & (fo::CHUNK - 1));
-    const uint64_t n_chunks = fo::chunk_count(a, total), blocks = (n_chunks + 255) / 256;
-    if (blocks > 0x7FFFFFFFull) {
-        c->err = "ranges: " + std::to_string(total) + " symbols are more than one launch maps to letters";
-        return AGC_HIP_EINVAL;
-    }
+    ChunkLaunch L;
+    L.add(d_out, total);
+    CHK(L.fits(c, "ranges: " + std::to_string(total) + " symbols are", "maps to letters"));
     if (n_wj) {
         CHK(ensure(c, c->rd.d_rg_jobs, (size_t)n_wj * sizeof(WindowJob)));
         CHK(upload(c, c->rd.d_rg_jobs.p, wj.data(), (size_t)n_wj * sizeof(WindowJob), c->stream));
@@ -367,7 +381,7 @@ int window_write(agc_hip_ctx *c, const std::vector<WindowJob> &wj, const std::ve
     }
     if (letters && total) {
         KTimer t(c, AGC_HIP_K_RANGES);
-        hipLaunchKernelGGL(letters_kernel, dim3((uint32_t)blocks), dim3(256), 0, c->stream, d_out, a, total, n_chunks);
+        hipLaunchKernelGGL(letters_kernel, dim3((uint32_t)L.blocks), dim3(256), 0, c->stream, d_out, L.a, total, L.n_chunks);
     }
     HIPCHK(c, hipGetLastError());
     return AGC_HIP_OK;
@@ -386,10 +400,8 @@ struct GzOut {
 int bgzf_capacity(agc_hip_ctx *c, const char *call, uint64_t n, const GzOut &G)
 {
     *G.h_len = bgzf::bound(n);
-    if (bgzf::block_count(n) > 0xFFFFFFFFull) {
-        c->err = std::string(call) + ": " + std::to_string(n) + " bytes are more than 2^32 - 1 blocks";
-        return AGC_HIP_EINVAL;
-    }
+    if (bgzf::block_count(n) > 0xFFFFFFFFull)
+        return refuse(c, std::string(call) + ": " + std::to_string(n) + " bytes are more than 2^32 - 1 blocks");
     return capacity_holds(c, call, "stream", G.cap, bgzf::bound(n));
 }
 
@@ -418,10 +430,8 @@ int bgzf_stage(agc_hip_ctx *c, const char *call, const uint8_t *d_in, uint64_t n
     }
     uint64_t at = 0;
     for (uint64_t b = 0; b < n_blocks; ++b) {
-        if (sizes[b] < bgzf::HEADER + bgzf::TRAILER || sizes[b] > bgzf::MEMBER_MAX) { // (no address is made of a size no member can have)
-            c->err = std::string(call) + ": block " + std::to_string(b) + " came back with a member of " + std::to_string(sizes[b]) + " bytes";
-            return AGC_HIP_ENODEV;
-        }
+        if (sizes[b] < bgzf::HEADER + bgzf::TRAILER || sizes[b] > bgzf::MEMBER_MAX) // (no address is made of a size no member can have)
+            return refuse(c, std::string(call) + ": block " + std::to_string(b) + " came back with a member of " + std::to_string(sizes[b]) + " bytes", AGC_HIP_ENODEV);
         off[b] = at;
         at += sizes[b];
     }
@@ -452,64 +462,129 @@ const char *part_refusal(uint32_t status)
     return status == pu::ZSTD_UNSUPPORTED ? "an unsupported zstd frame (status 1)" : status == pu::ZSTD_MALFORMED ? "a malformed zstd frame (status 2)" : "a malformed tuple stream (status 3)";
 }
 
-// the REF_* parts of a call are NEW references: each of a group that is not registered and that no other part names; new_ref: group ->
-// its part.  With any of them, min_match_len must be one agc_hip_ref_register takes
-int new_references(agc_hip_ctx *c, const char *call, uint32_t n_parts, const agc_hip_part *h_parts, uint32_t min_match_len, std::map<uint32_t, uint32_t> &new_ref)
-{
-    auto registered = [c](uint32_t gid) { return gid < c->refs.size() && c->refs[gid].valid; };
-    for (uint32_t i = 0; i < n_parts; ++i)
-        if (h_parts[i].content != AGC_HIP_PART_PACK) {
-            const uint32_t g = h_parts[i].gid;
-            if (registered(g) || !new_ref.emplace(g, i).second) {
-                c->err = std::string(call) + ": part " + std::to_string(i) + " is a reference of group " + std::to_string(g) + ", which " +
-                         (registered(g) ? "is registered already" : "another part is a reference of as well");
-                return AGC_HIP_EINVAL;
+// ---- a call that reads from archive parts -------------------------------------------------------------------------------------------
+// Steps 2 to 5 of agc_hip_sample_fasta_parts and agc_hip_ranges_parts (include/agc_hip.h), whose order is the contract: a group
+// registers once, so no reference is registered until nothing can be refused any more.  A call makes one PartsCall and calls, in this
+// order, check() -> unpack() -> its own layout, which may still refuse (locate() and ref_size() serve it) -> register_refs().
+// Item: agc_hip_seg_part or agc_hip_seg_win (kind, gid, part, index, length, rc in front); noun: what a message calls one.
+template <class Item> struct PartsCall {
+    agc_hip_ctx *c;
+    const char *call, *noun;
+    uint32_t n_parts;
+    const agc_hip_part *h_parts;
+    const uint8_t *h_src;
+    uint64_t src_bytes;
+    uint32_t seq_cap, min_match_len;
+    uint64_t n_items;
+    const Item *h_items;
+    PartsState S;
+    std::map<uint32_t, uint32_t> new_ref; // group -> the part that is its NEW reference
+    int refuse(const std::string &what, int code = AGC_HIP_EINVAL) { return ::refuse(c, std::string(call) + ": " + what, code); }
+
+    // 2. Before any launch.  The parts as arguments; every REF_* part a new reference: of a group that is not registered and that no
+    // other part names, with a min_match_len agc_hip_ref_register takes.  Every item; then extra(item) -> nullptr, or what else is wrong.
+    template <class Extra> int check(Extra extra)
+    {
+        CHK(parts_check(c, call, n_parts, h_parts, src_bytes));
+        for (uint32_t i = 0; i < n_parts; ++i)
+            if (h_parts[i].content != AGC_HIP_PART_PACK) {
+                const uint32_t g = h_parts[i].gid;
+                if (registered(c, g) || !new_ref.emplace(g, i).second)
+                    return refuse("part " + std::to_string(i) + " is a reference of group " + std::to_string(g) + ", which " +
+                                  (registered(c, g) ? "is registered already" : "another part is a reference of as well"));
             }
+        if (!new_ref.empty() && (min_match_len < HASHING_STEP + 4 || min_match_len > 32))
+            return refuse("a min_match_len of " + std::to_string(min_match_len) + " registers no reference");
+        for (uint64_t i = 0; i < n_items; ++i) {
+            const Item &g = h_items[i];
+            const char *why;
+            int code = AGC_HIP_EINVAL;
+            if (g.kind > AGC_HIP_SEG_DELTA)
+                why = "has an unknown kind";
+            else if (g.kind != AGC_HIP_SEG_RAW && !registered(c, g.gid) && !new_ref.count(g.gid))
+                why = "names a group that has no registered reference and none among the parts", code = AGC_HIP_ENOREF;
+            else if (g.kind != AGC_HIP_SEG_REF && (g.part >= n_parts || h_parts[g.part].content != AGC_HIP_PART_PACK))
+                why = "names a part that is not a pack of the batch";
+            else
+                why = extra(g);
+            if (why)
+                return refuse(std::string(noun) + " " + std::to_string(i) + " " + why, code);
         }
-    if (!new_ref.empty() && (min_match_len < HASHING_STEP + 4 || min_match_len > 32)) {
-        c->err = std::string(call) + ": a min_match_len of " + std::to_string(min_match_len) + " registers no reference";
-        return AGC_HIP_EINVAL;
+        return AGC_HIP_OK;
     }
+
+    // 3. The parts, unpacked on the device, and (4) what it found of them.  Nothing is registered or written yet.
+    int unpack()
+    {
+        HIPCHK(c, hipSetDevice(c->device));
+        if (n_parts)
+            CHK(parts_decode_index(c, n_parts, h_parts, h_src, seq_cap, S));
+        for (uint32_t i = 0; i < n_parts; ++i)
+            if (S.status(i) != pu::OK || (h_parts[i].content != AGC_HIP_PART_PACK && S.info[i].n > 0xFFFFFFFFull))
+                return refuse("part " + std::to_string(i) + " is refused: " + (S.status(i) != pu::OK ? part_refusal(S.status(i)) : "a reference of 2^32 symbols or more"));
+        return AGC_HIP_OK;
+    }
+
+    // (4, for the call's layout) the sequence of RAW / DELTA item i, as bytes of d_pu_dec; EINVAL: its index is out of reach
+    int locate(uint64_t i, uint64_t &off, uint32_t &n)
+    {
+        std::string why;
+        return S.locate(h_items[i].part, h_items[i].index, off, n, why) ? AGC_HIP_OK : refuse(std::string(noun) + " " + std::to_string(i) + " is " + why);
+    }
+    // the symbols of a group's reference, new (as unpack() found it) or registered; -1: it has none
+    int64_t ref_size(uint32_t gid) const { return new_ref.count(gid) ? (int64_t)S.info[new_ref.at(gid)].n : registered_size(c, gid); }
+
+    // 5. The new references' symbols back to back (16-byte aligned) in the context's buffer, registered in one batch from there.
+    int register_refs()
+    {
+        if (new_ref.empty())
+            return AGC_HIP_OK;
+        std::vector<UnpackJob> wj;
+        std::vector<uint32_t> gid, len;
+        std::vector<uint64_t> off;
+        uint64_t tot = 0;
+        for (const auto &gr : new_ref) {
+            const PartJob &j = S.jobs[gr.second];
+            const PartInfo &f = S.info[gr.second];
+            gid.push_back(gr.first), off.push_back(tot), len.push_back((uint32_t)f.n);
+            if (f.n)
+                wj.push_back({j.dec_off, tot, f.n, 0, f.count, 0});
+            tot += (f.n + 15) & ~(uint64_t)15;
+        }
+        CHK(ensure(c, c->rd.d_pu_out, tot + 64));
+        CHK(unpack_write(c, wj, c->rd.d_pu_out.as<uint8_t>()));
+        return agc_hip_ref_register_batch_dev(c, (uint32_t)gid.size(), gid.data(), c->rd.d_pu_out.as<uint8_t>(), off.data(), len.data(), nullptr, min_match_len);
+    }
+};
+
+// The prelude of the two LZ decode calls, n >= 1 deltas: every group registered and the offsets ascending, or nothing is launched;
+// then the jobs (their outputs not laid out yet), the deltas into d_dec_enc, the scan stage -- and the first delta it rejects.
+int scan_delta_batch(agc_hip_ctx *c, const char *call, uint32_t n, const uint32_t *h_gid, const uint8_t *h_enc, const uint64_t *h_enc_off, const uint8_t *h_rc,
+                     std::vector<DecodeJob> &jobs, std::vector<DecodeResult> &res)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!registered(c, h_gid[i]))
+            return refuse(c, std::string(call) + ": delta " + std::to_string(i) + ": group " + std::to_string(h_gid[i]) + " has no registered reference");
+        CHK(offsets_ascend(c, call, "delta", h_enc_off, i));
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(upload_refs(c));
+    const uint64_t e0 = h_enc_off[0], enc_bytes = h_enc_off[n] - e0;
+    jobs.resize(n);
+    for (uint32_t i = 0; i < n; ++i)
+        jobs[i] = {h_enc_off[i] - e0, h_enc_off[i + 1] - h_enc_off[i], 0, 0, h_gid[i], h_rc && h_rc[i] ? 1u : 0u, 0};
+    CHK(ensure(c, c->rd.d_dec_enc, enc_bytes + 64));
+    if (enc_bytes)
+        CHK(upload(c, c->rd.d_dec_enc.p, h_enc + e0, enc_bytes, c->stream));
+    CHK(decode_scan(c, jobs, c->rd.d_dec_enc.as<uint8_t>(), res));
+    for (uint32_t i = 0; i < n; ++i)
+        if (res[i].status != lzd::OK)
+            return refuse(c, std::string(call) + ": delta " + std::to_string(i) + " is rejected: " + delta_refusal(res[i].status));
     return AGC_HIP_OK;
 }
 
-// a segment named by its part (agc_hip_seg_part's fields) against the parts; has_ref: its group is registered or among the new
-// references.  -> nullptr, or what is wrong with it (code: AGC_HIP_EINVAL / AGC_HIP_ENOREF)
-const char *seg_part_refusal(uint32_t kind, uint32_t part, uint32_t n_parts, const agc_hip_part *h_parts, bool has_ref, int &code)
-{
-    code = AGC_HIP_EINVAL;
-    if (kind > AGC_HIP_SEG_DELTA)
-        return "has an unknown kind";
-    if (kind != AGC_HIP_SEG_RAW && !has_ref) {
-        code = AGC_HIP_ENOREF;
-        return "names a group that has no registered reference and none among the parts";
-    }
-    if (kind != AGC_HIP_SEG_REF && (part >= n_parts || h_parts[part].content != AGC_HIP_PART_PACK))
-        return "names a part that is not a pack of the batch";
-    return nullptr;
-}
-
-// the new references' symbols back to back (16-byte aligned) in the context's buffer, registered in one batch from there
-int register_new_references(agc_hip_ctx *c, const PartsState &S, const std::map<uint32_t, uint32_t> &new_ref, uint32_t min_match_len)
-{
-    if (new_ref.empty())
-        return AGC_HIP_OK;
-    std::vector<UnpackJob> wj;
-    std::vector<uint32_t> gid, len;
-    std::vector<uint64_t> off;
-    uint64_t tot = 0;
-    for (const auto &gr : new_ref) {
-        const PartJob &j = S.jobs[gr.second];
-        const PartInfo &f = S.info[gr.second];
-        gid.push_back(gr.first), off.push_back(tot), len.push_back((uint32_t)f.n);
-        if (f.n)
-            wj.push_back({j.dec_off, tot, f.n, 0, f.count, 0});
-        tot += (f.n + 15) & ~(uint64_t)15;
-    }
-    CHK(ensure(c, c->rd.d_pu_out, tot + 64));
-    CHK(unpack_write(c, wj, c->rd.d_pu_out.as<uint8_t>()));
-    return agc_hip_ref_register_batch_dev(c, (uint32_t)gid.size(), gid.data(), c->rd.d_pu_out.as<uint8_t>(), off.data(), len.data(), nullptr, min_match_len);
-}
+// the job records range_plan.h and fasta_plan.h fill member by member, and tests/ranges_host and tests/fastaout_host mirror
+static_assert(sizeof(DecodeJob) == 40 && sizeof(WindowJob) == 40 && sizeof(WindowCopyJob) == 40 && sizeof(CopyJob) == 32, "a job record changed: its CPU mirrors must follow");
 
 } // namespace
 
@@ -524,29 +599,9 @@ static int lz_decode_impl(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, con
     h_out_off[0] = 0;
     if (!n)
         return AGC_HIP_OK;
-    for (uint32_t i = 0; i < n; ++i) {
-        if (h_gid[i] >= c->refs.size() || !c->refs[h_gid[i]].valid) {
-            c->err = "lz_decode: delta " + std::to_string(i) + ": group " + std::to_string(h_gid[i]) + " has no registered reference";
-            return AGC_HIP_EINVAL;
-        }
-        CHK(offsets_ascend(c, "lz_decode", "delta", h_enc_off, i));
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    CHK(upload_refs(c));
-    const uint64_t e0 = h_enc_off[0], enc_bytes = h_enc_off[n] - e0;
-    std::vector<DecodeJob> jobs(n);
-    for (uint32_t i = 0; i < n; ++i)
-        jobs[i] = {h_enc_off[i] - e0, h_enc_off[i + 1] - h_enc_off[i], 0, 0, h_gid[i], h_rc && h_rc[i] ? 1u : 0u, 0};
-    CHK(ensure(c, c->rd.d_dec_enc, enc_bytes + 64));
-    if (enc_bytes)
-        CHK(upload(c, c->rd.d_dec_enc.p, h_enc + e0, enc_bytes, c->stream));
+    std::vector<DecodeJob> jobs;
     std::vector<DecodeResult> res;
-    CHK(decode_scan(c, jobs, c->rd.d_dec_enc.as<uint8_t>(), res));
-    for (uint32_t i = 0; i < n; ++i)
-        if (res[i].status != lzd::OK) {
-            c->err = "lz_decode: delta " + std::to_string(i) + " is rejected: " + delta_refusal(res[i].status);
-            return AGC_HIP_EINVAL;
-        }
+    CHK(scan_delta_batch(c, "lz_decode", n, h_gid, h_enc, h_enc_off, h_rc, jobs, res));
     uint64_t tot = 0;
     for (uint32_t i = 0; i < n; ++i) {
         h_out_off[i] = tot;
@@ -576,16 +631,12 @@ static int sample_fasta_impl(agc_hip_ctx *c, uint32_t n_ctg, const uint64_t *h_c
     *h_text_len = 0;
     if (!n_ctg)
         return AGC_HIP_OK;
-    const auto Y = fp::lay_out_sample<DecodeJob, CopyJob>(n_ctg, h_ctg_seg, h_seg, n_bytes, k, line_length, h_name_off, [c](uint32_t gid) {
-        return gid < c->refs.size() && c->refs[gid].valid ? (int64_t)c->refs[gid].ref_size : (int64_t)-1;
-    });
+    const auto Y = fp::lay_out_sample<DecodeJob, CopyJob>(n_ctg, h_ctg_seg, h_seg, n_bytes, k, line_length, h_name_off, [c](uint32_t gid) { return registered_size(c, gid); });
     *h_text_len = Y.text;
-    if (Y.code != AGC_HIP_OK) {
-        c->err = Y.why;
-        return Y.code;
-    }
+    if (Y.code != AGC_HIP_OK)
+        return refuse(c, Y.why, Y.code);
     CHK(capacity_holds(c, "sample_fasta", "text", text_cap, Y.text));
-    TextLaunch T;
+    ChunkLaunch T;
     CHK(text_launch(c, d_text, Y.text, T));
     HIPCHK(c, hipSetDevice(c->device));
     CHK(ensure(c, c->rd.d_dec_enc, n_bytes + 64));
@@ -639,10 +690,8 @@ static int zstd_decode_impl(agc_hip_ctx *c, uint32_t n, const uint8_t *h_src, co
         if (h_status)
             h_status[i] = status[i];
     for (uint32_t i = 0; i < n; ++i)
-        if (status[i] != zs::dec::OK) {
-            c->err = "zstd_decode: frame " + std::to_string(i) + " is refused: " + (status[i] == zs::dec::UNSUPPORTED ? "unsupported (status 1)" : "malformed (status 2)");
-            return AGC_HIP_EINVAL;
-        }
+        if (status[i] != zs::dec::OK)
+            return refuse(c, "zstd_decode: frame " + std::to_string(i) + " is refused: " + (status[i] == zs::dec::UNSUPPORTED ? "unsupported (status 1)" : "malformed (status 2)"));
     return AGC_HIP_OK;
 }
 
@@ -690,10 +739,8 @@ static int parts_unpack_impl(agc_hip_ctx *c, uint32_t n, const agc_hip_part *h_p
         CHK(hand_back(c, h_out, d_out, tot));
     }
     for (uint32_t i = 0; i < n; ++i)
-        if (h_status[i] != pu::OK) {
-            c->err = "parts_unpack: part " + std::to_string(i) + " is refused: " + part_refusal(h_status[i]);
-            return AGC_HIP_EINVAL;
-        }
+        if (h_status[i] != pu::OK)
+            return refuse(c, "parts_unpack: part " + std::to_string(i) + " is refused: " + part_refusal(h_status[i]));
     return AGC_HIP_OK;
 }
 
@@ -721,67 +768,34 @@ static int sample_fasta_parts_impl(agc_hip_ctx *c, uint32_t n_parts, const agc_h
     }
     // 1. the text's size
     uint64_t text = 0;
-    if (!fp::plan_text_bytes(n_ctg, h_ctg_seg, k, line_length, h_name_off, [h_seg](uint64_t s) { return h_seg[s].length; }, text)) {
-        c->err = std::string(call) + ": the contigs' segment ranges or name offsets do not ascend from 0";
-        return AGC_HIP_EINVAL;
-    }
+    if (!fp::plan_text_bytes(n_ctg, h_ctg_seg, k, line_length, h_name_off, [h_seg](uint64_t s) { return h_seg[s].length; }, text))
+        return refuse(c, std::string(call) + ": the contigs' segment ranges or name offsets do not ascend from 0");
     *h_text_len = text;
     if (gz) {
         CHK(bgzf_capacity(c, call, text, *gz));
         h_text = d_text = nullptr;
     } else
         CHK(capacity_holds(c, call, "text", text_cap, text));
-    TextLaunch T;
+    ChunkLaunch T;
     CHK(text_launch(c, d_text, text, T));
-    // 2. the plan against the parts and the context
-    CHK(parts_check(c, call, n_parts, h_parts, src_bytes));
-    auto registered = [c](uint32_t gid) { return gid < c->refs.size() && c->refs[gid].valid; };
-    std::map<uint32_t, uint32_t> new_ref; // group -> its part
-    CHK(new_references(c, call, n_parts, h_parts, min_match_len, new_ref));
+    // 2. the plan against the parts and the context; 3. the parts, unpacked on the device
     const uint64_t n_seg = h_ctg_seg[n_ctg];
-    for (uint64_t s = 0; s < n_seg; ++s) {
-        const agc_hip_seg_part &g = h_seg[s];
-        int code = AGC_HIP_EINVAL;
-        const char *why = seg_part_refusal(g.kind, g.part, n_parts, h_parts, registered(g.gid) || new_ref.count(g.gid), code);
-        if (why) {
-            c->err = std::string(call) + ": segment " + std::to_string(s) + " " + why;
-            return code;
-        }
-    }
-    // 3. the parts, unpacked on the device
-    HIPCHK(c, hipSetDevice(c->device));
-    PartsState S;
-    if (n_parts)
-        CHK(parts_decode_index(c, n_parts, h_parts, h_src, seq_cap, S));
-    // 4. what the device found, against the plan; the layout with the new references' sizes -- nothing is registered or written yet
-    for (uint32_t i = 0; i < n_parts; ++i)
-        if (S.status(i) != pu::OK || (h_parts[i].content != AGC_HIP_PART_PACK && S.info[i].n > 0xFFFFFFFFull)) {
-            c->err = std::string(call) + ": part " + std::to_string(i) + " is refused: " + (S.status(i) != pu::OK ? part_refusal(S.status(i)) : "a reference of 2^32 symbols or more");
-            return AGC_HIP_EINVAL;
-        }
+    PartsCall<agc_hip_seg_part> P = {c, call, "segment", n_parts, h_parts, h_src, src_bytes, seq_cap, min_match_len, n_seg, h_seg};
+    CHK(P.check([](const agc_hip_seg_part &) -> const char * { return nullptr; })); // (a segment has no further check)
+    CHK(P.unpack());
+    // 4. the layout, with the sequences where the device found them and the new references' sizes
     std::vector<agc_hip_seg_src> seg(n_seg);
     for (uint64_t s = 0; s < n_seg; ++s) {
         const agc_hip_seg_part &g = h_seg[s];
         seg[s] = {g.kind, g.gid, 0, 0, g.length, g.rc, 0};
-        if (g.kind == AGC_HIP_SEG_REF)
-            continue;
-        if (g.index >= S.info[g.part].count || g.index >= seq_cap) {
-            c->err = std::string(call) + ": segment " + std::to_string(s) + " is sequence " + std::to_string(g.index) + " of part " + std::to_string(g.part) + ", which has " +
-                     std::to_string(S.info[g.part].count) + " (at most " + std::to_string(seq_cap) + " are indexed)";
-            return AGC_HIP_EINVAL;
-        }
-        S.sequence(g.part, g.index, seg[s].off, seg[s].n_bytes);
+        if (g.kind != AGC_HIP_SEG_REF)
+            CHK(P.locate(s, seg[s].off, seg[s].n_bytes));
     }
-    const SampleLayout Y = fp::lay_out_sample<DecodeJob, CopyJob>(n_ctg, h_ctg_seg, seg.data(), S.dec_bytes, k, line_length, h_name_off, [&](uint32_t gid) {
-        const auto it = new_ref.find(gid);
-        return it != new_ref.end() ? (int64_t)S.info[it->second].n : registered(gid) ? (int64_t)c->refs[gid].ref_size : (int64_t)-1;
-    });
-    if (Y.code != AGC_HIP_OK) {
-        c->err = Y.why;
-        return Y.code;
-    }
+    const SampleLayout Y = fp::lay_out_sample<DecodeJob, CopyJob>(n_ctg, h_ctg_seg, seg.data(), P.S.dec_bytes, k, line_length, h_name_off, [&P](uint32_t gid) { return P.ref_size(gid); });
+    if (Y.code != AGC_HIP_OK)
+        return refuse(c, Y.why, Y.code);
     // 5. the new references, registered in one batch from the device buffer
-    CHK(register_new_references(c, S, new_ref, min_match_len));
+    CHK(P.register_refs());
     // 6. agc_hip_sample_fasta's path, the deltas and raw symbols read where the parts stage left them
     CHK(write_sample(c, Y, c->rd.d_pu_dec.as<uint8_t>(), n_ctg, h_ctg_seg, h_names, h_name_off, line_length, h_text, d_text, T));
     // 7. (gz) the text, which write_sample left in the context's buffer, into the stream
@@ -821,39 +835,17 @@ static int lz_decode_window_impl(agc_hip_ctx *c, uint32_t n, const uint32_t *h_g
     }
     h_out_off[n] = tot;
     CHK(capacity_holds(c, call, "output", out_cap, tot));
-    for (uint32_t i = 0; i < n; ++i) {
-        if (!h_win_len[i]) {
-            c->err = std::string(call) + ": delta " + std::to_string(i) + " has a window of no symbols";
-            return AGC_HIP_EINVAL;
-        }
-        if (h_gid[i] >= c->refs.size() || !c->refs[h_gid[i]].valid) {
-            c->err = std::string(call) + ": delta " + std::to_string(i) + ": group " + std::to_string(h_gid[i]) + " has no registered reference";
-            return AGC_HIP_EINVAL;
-        }
-        CHK(offsets_ascend(c, call, "delta", h_enc_off, i));
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    CHK(upload_refs(c));
-    const uint64_t e0 = h_enc_off[0], enc_bytes = h_enc_off[n] - e0;
-    std::vector<DecodeJob> jobs(n);
     for (uint32_t i = 0; i < n; ++i)
-        jobs[i] = {h_enc_off[i] - e0, h_enc_off[i + 1] - h_enc_off[i], 0, 0, h_gid[i], h_rc && h_rc[i] ? 1u : 0u, 0};
-    CHK(ensure(c, c->rd.d_dec_enc, enc_bytes + 64));
-    if (enc_bytes)
-        CHK(upload(c, c->rd.d_dec_enc.p, h_enc + e0, enc_bytes, c->stream));
+        if (!h_win_len[i])
+            return refuse(c, std::string(call) + ": delta " + std::to_string(i) + " has a window of no symbols");
+    std::vector<DecodeJob> jobs;
     std::vector<DecodeResult> res;
-    CHK(decode_scan(c, jobs, c->rd.d_dec_enc.as<uint8_t>(), res));
+    CHK(scan_delta_batch(c, call, n, h_gid, h_enc, h_enc_off, h_rc, jobs, res));
     std::vector<WindowJob> wj(n);
     for (uint32_t i = 0; i < n; ++i) {
-        if (res[i].status != lzd::OK) {
-            c->err = std::string(call) + ": delta " + std::to_string(i) + " is rejected: " + delta_refusal(res[i].status);
-            return AGC_HIP_EINVAL;
-        }
-        if (!rp::window_fits(h_win_from[i], h_win_len[i], res[i].len)) {
-            c->err = std::string(call) + ": delta " + std::to_string(i) + " decodes to " + std::to_string(res[i].len) + " symbols, its window [" +
-                     std::to_string(h_win_from[i]) + ", +" + std::to_string(h_win_len[i]) + ") reaches past them";
-            return AGC_HIP_EINVAL;
-        }
+        if (!rp::window_fits(h_win_from[i], h_win_len[i], res[i].len))
+            return refuse(c, std::string(call) + ": delta " + std::to_string(i) + " decodes to " + std::to_string(res[i].len) + " symbols, its window [" +
+                                 std::to_string(h_win_from[i]) + ", +" + std::to_string(h_win_len[i]) + ") reaches past them");
         wj[i] = {jobs[i].enc_off, jobs[i].enc_len, h_out_off[i], 0, 0, jobs[i].ref_slot, jobs[i].rc};
         rw::decode_window(h_win_from[i], h_win_len[i], res[i].len, jobs[i].rc, wj[i].w_lo, wj[i].w_hi);
     }
@@ -876,105 +868,35 @@ static int ranges_parts_impl(agc_hip_ctx *c, uint32_t n_parts, const agc_hip_par
     if (!n_q)
         return AGC_HIP_OK;
     // 1. the output's layout
-    const uint64_t n_win = h_q_seg[n_q];
-    bool ascending = h_q_seg[0] == 0 && n_win <= 0xFFFFFFFFull;
-    for (uint32_t q = 0; q < n_q; ++q)
-        ascending = ascending && h_q_seg[q] <= h_q_seg[q + 1] && h_q_seg[q + 1] <= n_win;
-    if (!ascending) {
-        c->err = std::string(call) + ": the queries' window ranges do not ascend from 0";
-        return AGC_HIP_EINVAL;
-    }
-    std::vector<uint64_t> win_out(n_win); // where every window goes
+    std::vector<uint64_t> win_out; // where every window goes
     uint64_t tot = 0;
-    for (uint32_t q = 0; q < n_q; ++q) {
-        h_out_off[q] = tot;
-        for (uint64_t w = h_q_seg[q]; w < h_q_seg[q + 1]; ++w) {
-            win_out[w] = tot;
-            tot += h_win[w].win_len;
-        }
-    }
-    h_out_off[n_q] = tot;
+    if (!rp::lay_out_queries(n_q, h_q_seg, h_win, h_out_off, win_out, tot))
+        return refuse(c, std::string(call) + ": the queries' window ranges do not ascend from 0");
     CHK(capacity_holds(c, call, "output", out_cap, tot));
-    // 2. the plan against the parts and the context
-    CHK(parts_check(c, call, n_parts, h_parts, src_bytes));
-    auto registered = [c](uint32_t gid) { return gid < c->refs.size() && c->refs[gid].valid; };
-    std::map<uint32_t, uint32_t> new_ref; // group -> its part
-    CHK(new_references(c, call, n_parts, h_parts, min_match_len, new_ref));
-    for (uint64_t w = 0; w < n_win; ++w) {
-        const agc_hip_seg_win &g = h_win[w];
-        int code = AGC_HIP_EINVAL;
-        const char *why = seg_part_refusal(g.kind, g.part, n_parts, h_parts, registered(g.gid) || new_ref.count(g.gid), code);
-        if (!why && !rp::window_fits(g.win_from, g.win_len, g.length))
-            why = g.win_len ? "reaches past its segment's length" : "has no symbols";
-        if (why) {
-            c->err = std::string(call) + ": window " + std::to_string(w) + " " + why;
-            return code;
-        }
-    }
+    // 2. the plan against the parts and the context, every window against its segment
+    const uint64_t n_win = h_q_seg[n_q];
+    PartsCall<agc_hip_seg_win> P = {c, call, "window", n_parts, h_parts, h_src, src_bytes, seq_cap, min_match_len, n_win, h_win};
+    CHK(P.check([](const agc_hip_seg_win &g) -> const char * {
+        return rp::window_fits(g.win_from, g.win_len, g.length) ? nullptr : g.win_len ? "reaches past its segment's length" : "has no symbols";
+    }));
     if (!n_win)
         return AGC_HIP_OK;
     // 3. the parts, unpacked on the device
-    HIPCHK(c, hipSetDevice(c->device));
-    PartsState S;
-    if (n_parts)
-        CHK(parts_decode_index(c, n_parts, h_parts, h_src, seq_cap, S));
-    // 4. what the device found, against the plan -- nothing is registered or written yet
-    for (uint32_t i = 0; i < n_parts; ++i)
-        if (S.status(i) != pu::OK || (h_parts[i].content != AGC_HIP_PART_PACK && S.info[i].n > 0xFFFFFFFFull)) {
-            c->err = std::string(call) + ": part " + std::to_string(i) + " is refused: " + (S.status(i) != pu::OK ? part_refusal(S.status(i)) : "a reference of 2^32 symbols or more");
-            return AGC_HIP_EINVAL;
-        }
-    std::vector<DecodeJob> dj;
-    std::vector<WindowJob> wj;
-    std::vector<uint64_t> dj_win;
-    std::vector<WindowCopyJob> cj;
-    for (uint64_t w = 0; w < n_win; ++w) {
-        const agc_hip_seg_win &g = h_win[w];
-        const uint32_t rc = g.rc ? 1u : 0u;
-        uint64_t off = 0;
-        uint32_t n = 0;
-        if (g.kind != AGC_HIP_SEG_REF) {
-            if (g.index >= S.info[g.part].count || g.index >= seq_cap) {
-                c->err = std::string(call) + ": window " + std::to_string(w) + " is of sequence " + std::to_string(g.index) + " of part " + std::to_string(g.part) +
-                         ", which has " + std::to_string(S.info[g.part].count) + " (at most " + std::to_string(seq_cap) + " are indexed)";
-                return AGC_HIP_EINVAL;
-            }
-            S.sequence(g.part, g.index, off, n);
-        }
-        if (g.kind == AGC_HIP_SEG_DELTA) {
-            dj.push_back({off, n, 0, g.length, g.gid, rc, 0});
-            dj_win.push_back(w);
-            WindowJob j = {off, n, win_out[w], 0, 0, g.gid, rc};
-            rw::decode_window(g.win_from, g.win_len, g.length, rc, j.w_lo, j.w_hi);
-            wj.push_back(j);
-            continue;
-        }
-        const auto it = new_ref.find(g.gid);
-        const uint64_t have = g.kind == AGC_HIP_SEG_RAW ? n : it != new_ref.end() ? S.info[it->second].n : c->refs[g.gid].ref_size;
-        if (have != g.length) {
-            c->err = std::string(call) + ": window " + std::to_string(w) + " is of a " + (g.kind == AGC_HIP_SEG_RAW ? "raw sequence" : "reference") + " of " +
-                     std::to_string(have) + " symbols, its length says " + std::to_string(g.length);
-            return AGC_HIP_EINVAL;
-        }
-        cj.push_back({off, win_out[w], g.length, g.win_from, g.win_len, g.gid, rc, g.kind == AGC_HIP_SEG_REF ? 1u : 0u});
-    }
+    CHK(P.unpack());
+    // 4. the windows' jobs, with the sequences where the device found them and the new references' sizes
+    const auto Y = rp::lay_out_windows<DecodeJob, WindowJob, WindowCopyJob>(
+        call, n_win, h_win, win_out.data(), [&P](uint32_t part, uint32_t index, uint64_t &off, uint32_t &n, std::string &why) { return P.S.locate(part, index, off, n, why); },
+        [&P](uint32_t gid) { return P.ref_size(gid); });
+    if (Y.code != AGC_HIP_OK)
+        return refuse(c, Y.why, Y.code);
     // 5. the new references, registered in one batch from the device buffer
-    CHK(register_new_references(c, S, new_ref, min_match_len));
+    CHK(P.register_refs());
     // 6. the deltas against their lengths, then every window to its place
     CHK(upload_refs(c));
     const uint8_t *d_bytes = c->rd.d_pu_dec.as<uint8_t>();
-    if (!dj.empty()) {
-        std::vector<DecodeResult> res;
-        CHK(decode_scan(c, dj, d_bytes, res));
-        for (size_t i = 0; i < dj.size(); ++i)
-            if (res[i].status != lzd::OK || res[i].len != dj[i].out_len) {
-                c->err = std::string(call) + ": window " + std::to_string(dj_win[i]) +
-                         (res[i].status != lzd::OK ? " is of a malformed delta" : " is of a delta that decodes to " + std::to_string(res[i].len) + " symbols, its length says " + std::to_string(dj[i].out_len));
-                return AGC_HIP_EINVAL;
-            }
-    }
+    CHK(scan_declared_lengths(c, call, "window", Y.dj, Y.dj_win, d_bytes));
     CHK(output_buffer(c, d_out, c->rd.d_rg_out, tot));
-    CHK(window_write(c, wj, cj, d_bytes, d_out, tot, letters != 0));
+    CHK(window_write(c, Y.wj, Y.cj, d_bytes, d_out, tot, letters != 0));
     return hand_back(c, h_out, d_out, tot);
 }
 
