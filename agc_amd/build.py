@@ -26,7 +26,7 @@ class _Locked:
         fcntl.flock(self.f, fcntl.LOCK_UN)
         self.f.close()
 LIB = os.path.join(HERE, "libagc_hip.so")
-SOURCES = ["api.hip", "read_api.hip", "range_kernels.hip", "bgzf_kernels.hip", "bgzf.h", "range_clip.h", "range_plan.h", "fasta_plan.h", "lz_plan.h", "lz_consts.h", "scan_kernels.hip", "pack_kernels.hip", "lz_kernels.hip", "splitters.hip", "zstd_kernels.hip", "seg_kernels.hip", "segments.hip", "lz_decode_kernels.hip", "lz_decode.h", "fasta_out_kernels.hip", "fasta_out.h",
+SOURCES = ["api.hip", "read_api.hip", "range_kernels.hip", "bgzf_kernels.hip", "bgzf.h", "inflate_kernels.hip", "inflate.h", "range_clip.h", "range_plan.h", "fasta_plan.h", "lz_plan.h", "lz_consts.h", "scan_kernels.hip", "pack_kernels.hip", "lz_kernels.hip", "splitters.hip", "zstd_kernels.hip", "seg_kernels.hip", "segments.hip", "lz_decode_kernels.hip", "lz_decode.h", "fasta_out_kernels.hip", "fasta_out.h",
            "zstd_decode_kernels.hip", "zstd/zs_decode.h", "parts_unpack_kernels.hip", "parts_unpack.h", "dev_common.h", "sym_view.h",
            "zstd/zs_common.h", "zstd/zs_opt.h", "zstd/zs_opt_sm.h", "zstd/zs_opt_grp.h", "zstd/zs_entropy.h", "zstd/zs_frame.h", "zstd/zs_params.h"]
 

@@ -16,8 +16,9 @@ OK, ENODEV, EINVAL, ENOMEM, ECAP, ENOREF = 0, -1, -2, -3, -4, -5
 K_SCAN, K_INDEX, K_ENCODE, K_ESTIMATE, K_COSTVEC, K_REVCOMP, K_PREPROCESS, K_REFSTORE = range(8)
 K_NAMES = ["scan", "index", "encode", "estimate", "costvec", "revcomp", "preprocess", "refstore", "zstd", "filter", "segments", "pack",
            "decode_scan", "decode_write", "fasta_out"]
-K_NAMES_MORE = ["zstd_decode", "parts_unpack", "ranges", "bgzf"]  # the slots from 15 on (K_NAMES stays the 15 slots its users count on); timing_get reports both
+K_NAMES_MORE = ["zstd_decode", "parts_unpack", "ranges", "bgzf", "inflate"]  # the slots from 15 on (K_NAMES stays the 15 slots its users count on); timing_get reports both
 ZD_OK, ZD_UNSUPPORTED, ZD_MALFORMED = 0, 1, 2
+INF_OK, INF_UNSUPPORTED, INF_MALFORMED = 0, 1, 2
 SEG_RAW, SEG_REF, SEG_DELTA = 0, 1, 2
 PART_STORED, PART_ZSTD = 0, 1
 PART_PACK, PART_REF_BYTES, PART_REF_TUPLES = 0, 1, 2
@@ -40,6 +41,7 @@ SYMBOLS = [
     "agc_hip_parts_unpack", "agc_hip_parts_unpack_dev", "agc_hip_sample_fasta_parts", "agc_hip_sample_fasta_parts_dev",
     "agc_hip_ranges_parts", "agc_hip_ranges_parts_dev",
     "agc_hip_bgzf_bound", "agc_hip_bgzf", "agc_hip_bgzf_dev", "agc_hip_sample_fasta_parts_bgzf", "agc_hip_sample_fasta_parts_bgzf_dev",
+    "agc_hip_bgzf_members", "agc_hip_bgzf_inflate", "agc_hip_bgzf_inflate_dev",
     "agc_hip_host_alloc", "agc_hip_host_free",
     "agc_hip_lz_estimate_batch_dev", "agc_hip_lz_estimate_batch",
     "agc_hip_lz_cost_vector_batch_dev", "agc_hip_lz_cost_vector_batch",
@@ -188,6 +190,9 @@ def load():
     L.agc_hip_bgzf_bound.argtypes = [C.c_uint64]
     L.agc_hip_bgzf.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p]
     L.agc_hip_bgzf_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p]
+    L.agc_hip_bgzf_members.argtypes = [vp, C.c_uint64, u64p, u64p]
+    L.agc_hip_bgzf_inflate.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, u32p]
+    L.agc_hip_bgzf_inflate_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, u32p]
     L.agc_hip_zstd17_max_input.restype = C.c_uint32
     L.agc_hip_zstd17_resident_frames.argtypes = [vp]
     L.agc_hip_zstd17_resident_frames.restype = C.c_uint32
@@ -841,6 +846,44 @@ class Context:
         rc_, ln = self.bgzf_raw(d_in, n, d_out, out_cap, dev=True, block_off=off)
         self._chk(rc_)
         return ln, off
+
+    @staticmethod
+    def bgzf_members(data):
+        """the walk of a BGZF stream alone (agc_hip_bgzf_members, no context) -> (return code, members, text bytes): OK, or EINVAL at
+        the walk's first complaint with the members in front of it"""
+        d = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else _a(data, np.uint8)
+        nm, tb = C.c_uint64(0), C.c_uint64(0)
+        rc_ = load().agc_hip_bgzf_members(d.ctypes.data if d.size else None, d.size, C.byref(nm), C.byref(tb))
+        return rc_, nm.value, tb.value
+
+    def bgzf_inflate_raw(self, data, out_ptr, out_cap, dev=False):
+        """the entry point itself (agc_hip_bgzf_inflate, dev: _dev; out_ptr: an address or None) -> (return code, text length,
+        text_off[members + 1], statuses[members]) -- after a complaint of the walk the statuses end with the refused member's"""
+        d = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else _a(data, np.uint8)
+        _rc, nm, _tb = self.bgzf_members(d)
+        off, st = np.zeros(nm + 2, np.uint64), np.zeros(nm + 1, np.uint32)
+        ln = C.c_uint64(0)
+        fn = self.L.agc_hip_bgzf_inflate_dev if dev else self.L.agc_hip_bgzf_inflate
+        rc_ = fn(self.h, d.ctypes.data if d.size else None, d.size, out_ptr, int(out_cap), C.byref(ln), _p(off, u64p), _p(st, u32p))
+        return rc_, ln.value, off[:nm + 1], (st if _rc != OK else st[:nm])
+
+    def bgzf_inflate(self, data):
+        """a BGZF stream (bytes-like) -> its bytes; a refused member raises, the error naming it"""
+        _rc, _nm, tb = self.bgzf_members(data)
+        out = np.empty(max(tb, 1), np.uint8)
+        rc_, ln, _off, _st = self.bgzf_inflate_raw(data, out.ctypes.data, tb)
+        self._chk(rc_)
+        return out[:ln].tobytes()
+
+    def bgzf_inflate_dev(self, data):
+        """a BGZF stream (bytes-like, on the host) -> (its bytes as a torch uint8 tensor on the device, text_off[members + 1])"""
+        import torch
+        _rc, _nm, tb = self.bgzf_members(data)
+        out = torch.empty(max(tb, 1), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()  # (torch's allocation comes from torch's stream)
+        rc_, ln, off, _st = self.bgzf_inflate_raw(data, out.data_ptr(), tb, dev=True)
+        self._chk(rc_)
+        return out[:ln], off
 
     def ranges_parts_raw(self, parts, src, seq_cap, q_seg, wins, min_match_len, letters, out_ptr, out_cap, dev=False):
         """the entry point itself (agc_hip_ranges_parts, dev: _dev) -> (return code, out_off[n_q+1]); wins: SEG_WIN_DTYPE, query q =

@@ -31,6 +31,7 @@
 #include "parts_unpack_kernels.hip"
 #include "range_kernels.hip"
 #include "bgzf_kernels.hip"
+#include "inflate_kernels.hip"
 
 using namespace agc;
 
@@ -169,6 +170,7 @@ struct agc_hip_ctx {
         DevBuf d_pu_dec, d_pu_jobs, d_pu_res, d_pu_wjobs, d_pu_out; // agc_hip_parts_unpack*: the decoded parts, their descriptors, infos + end offsets, the write jobs, the final bytes
         DevBuf d_rg_jobs, d_rg_copy, d_rg_out; // agc_hip_lz_decode_window_batch*, agc_hip_ranges_parts*: the delta window jobs, the RAW / REF window jobs, the symbols
         DevBuf d_bz_in, d_bz_slots, d_bz_sizes, d_bz_off, d_bz_out; // agc_hip_bgzf*: the input, a slot of 65312 bytes per block, the members' sizes, their offsets, the stream
+        DevBuf d_inf_in, d_inf_jobs, d_inf_status, d_inf_out; // agc_hip_bgzf_inflate*: the stream, a job per member, the members' statuses, the bytes
     } rd;
 
     PackTemp pk1;        // byte-input entry points on the first stream

@@ -331,7 +331,7 @@ int main(int argc, char **argv)
     }
     if (kernel_times && c.HipContext()) {
         static const char *names[AGC_HIP_K_COUNT] = {"scan", "index", "encode", "estimate", "costvec", "revcomp", "preprocess", "refstore", "zstd", "filter",
-                                                     "segments", "pack", "decode_scan", "decode_write", "fasta_out", "zstd_decode", "parts_unpack", "ranges", "bgzf"};
+                                                     "segments", "pack", "decode_scan", "decode_write", "fasta_out", "zstd_decode", "parts_unpack", "ranges", "bgzf", "inflate"};
         const auto &s = c.Stats();
         std::cerr << "kernel-ms:";
         for (int w = 0; w < AGC_HIP_K_COUNT; ++w) {

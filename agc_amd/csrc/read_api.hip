@@ -3,7 +3,8 @@
 // (archive parts -> packs cut into sequences, references as symbols), agc_hip_sample_fasta_parts (a sample's archive parts -> its
 // FASTA text), agc_hip_lz_decode_window_batch (deltas -> a window of each one's symbols) and agc_hip_ranges_parts (archive parts -> a
 // batch of contig ranges), each with its _dev twin, and agc_hip_bgzf (bytes -> a BGZF stream) with agc_hip_sample_fasta_parts_bgzf (a
-// sample's archive parts -> its FASTA text as a BGZF stream).  All are built from the stages below.  The host arithmetic is not here:
+// sample's archive parts -> its FASTA text as a BGZF stream) and agc_hip_bgzf_inflate (a BGZF stream -> its bytes; the walk of the
+// stream and the decoder are inflate.h, the kernel inflate_kernels.hip).  All are built from the stages below.  The host arithmetic is not here:
 // layout, jobs and first complaint of a sample are fasta_plan.h's, of a range batch range_plan.h's (both run on the CPU in tests/);
 // this file checks arguments, uploads, launches and copies back.  The two calls from archive parts share PartsCall, the two LZ
 // decode calls scan_delta_batch.  Included by api.hip behind the create path (uses its context and helpers; the kernels are
@@ -450,6 +451,25 @@ int bgzf_stage(agc_hip_ctx *c, const char *call, const uint8_t *d_in, uint64_t n
     return hand_back(c, G.h_gz, d_out, total);
 }
 
+// The inflate stage: the stream lies in d_src already, walked by the host.  bgzf_inflate_kernel gives every member a wave and its
+// slice of d_out; the statuses stay in d_inf_status, one per member.
+int inflate_stage(agc_hip_ctx *c, const std::vector<inflate::Job> &jobs, const uint8_t *d_src, uint8_t *d_out)
+{
+    const uint32_t n = (uint32_t)jobs.size();
+    CHK(ensure(c, c->rd.d_inf_jobs, (size_t)n * sizeof(inflate::Job)));
+    CHK(ensure(c, c->rd.d_inf_status, (size_t)n * sizeof(uint32_t)));
+    CHK(upload(c, c->rd.d_inf_jobs.p, jobs.data(), (size_t)n * sizeof(inflate::Job), c->stream));
+    {
+        KTimer t(c, AGC_HIP_K_INFLATE);
+        hipLaunchKernelGGL(bgzf_inflate_kernel, dim3((n + INF_WAVES - 1) / INF_WAVES), dim3(INF_WAVES * WAVE), 0, c->stream, (const inflate::Job *)c->rd.d_inf_jobs.p, n, d_src,
+                           d_out, (uint32_t *)c->rd.d_inf_status.p); // a wave per member
+    }
+    HIPCHK(c, hipGetLastError());
+    return AGC_HIP_OK;
+}
+
+const char *inflate_refusal(uint32_t status) { return status == inflate::UNSUPPORTED ? "unsupported (status 1)" : "malformed (status 2)"; }
+
 const char *delta_refusal(uint32_t status)
 {
     static const char *why[] = {"", "a truncated or malformed token", "'!' at or past the end of the reference", "a match outside the reference",
@@ -817,6 +837,56 @@ static int bgzf_impl(agc_hip_ctx *c, const uint8_t *h_in, const uint8_t *d_in, u
     return bgzf_stage(c, "bgzf", d_in, n, G);
 }
 
+// A BGZF stream into its bytes.  The host walks the stream (inflate.h): that finds every member, sizes the output, and a stream the
+// walk complains about never reaches the device.  The inflate stage then gives every member a wave and its slice of the output.
+static int bgzf_inflate_impl(agc_hip_ctx *c, const uint8_t *h_in, uint64_t n, uint8_t *h_out, uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_len, uint64_t *h_text_off,
+                             uint32_t *h_status)
+{
+    if (!c || !h_out_len || (n && !h_in) || (out_cap && !h_out && !d_out))
+        return AGC_HIP_EINVAL;
+    inflate::Walk W;
+    inflate::walk(h_in, n, nullptr, 0, W);
+    if (W.n_members > 0xFFFFFFFFull)
+        return refuse(c, "bgzf_inflate: " + std::to_string(W.n_members) + " members are more than 2^32 - 1");
+    std::vector<inflate::Job> jobs(W.n_members);
+    inflate::Walk W2;
+    inflate::walk(h_in, n, jobs.data(), jobs.size(), W2);
+    const uint32_t n_mem = (uint32_t)jobs.size();
+    *h_out_len = W.text_bytes;
+    for (uint32_t m = 0; m < n_mem; ++m) {
+        if (h_text_off)
+            h_text_off[m] = jobs[m].out_off;
+        if (h_status)
+            h_status[m] = inflate::OK;
+    }
+    if (h_text_off)
+        h_text_off[n_mem] = W.text_bytes;
+    if (W.why != inflate::W_OK) {
+        if (h_status)
+            h_status[n_mem] = inflate::status_of(W.why);
+        return refuse(c, "bgzf_inflate: member " + std::to_string(n_mem) + " at byte " + std::to_string(W.at) + " is refused: " + inflate_refusal(inflate::status_of(W.why)));
+    }
+    CHK(capacity_holds(c, "bgzf_inflate", "output", out_cap, W.text_bytes));
+    if (!n_mem)
+        return AGC_HIP_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(ensure(c, c->rd.d_inf_in, n + 64));
+    // (an output of 0 bytes: the context's buffer stands in for a d_out the caller did not have to give)
+    CHK(output_buffer(c, d_out, c->rd.d_inf_out, W.text_bytes));
+    CHK(upload(c, c->rd.d_inf_in.p, h_in, n, c->stream));
+    CHK(inflate_stage(c, jobs, c->rd.d_inf_in.as<uint8_t>(), d_out));
+    std::vector<uint32_t> status(n_mem);
+    HIPCHK(c, hipMemcpyAsync(status.data(), c->rd.d_inf_status.p, (size_t)n_mem * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    CHK(hand_back(c, h_out, d_out, W.text_bytes));
+    for (uint32_t m = 0; m < n_mem; ++m)
+        if (h_status)
+            h_status[m] = status[m];
+    for (uint32_t m = 0; m < n_mem; ++m)
+        if (status[m] != inflate::OK)
+            return refuse(c, "bgzf_inflate: member " + std::to_string(m) + " is refused: " + inflate_refusal(status[m]));
+    return AGC_HIP_OK;
+}
+
 // The windowed LZ decode: the output's layout follows from the windows' sizes, so the capacity is looked at first; the scan stage
 // then checks every delta and says how long it is, and only when every window lies inside its delta is anything written.
 static int lz_decode_window_impl(agc_hip_ctx *c, uint32_t n, const uint32_t *h_gid, const uint8_t *h_enc, const uint64_t *h_enc_off, const uint8_t *h_rc,
@@ -912,6 +982,27 @@ int agc_hip_bgzf(agc_hip_ctx *c, const uint8_t *h_in, uint64_t n, uint8_t *h_out
 int agc_hip_bgzf_dev(agc_hip_ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_len, uint64_t *h_block_off)
 {
     return bgzf_impl(c, nullptr, d_in, n, {nullptr, d_out, out_cap, h_out_len, h_block_off});
+}
+
+int agc_hip_bgzf_members(const uint8_t *h_in, uint64_t n, uint64_t *h_n_members, uint64_t *h_text_bytes)
+{
+    if (!h_n_members || !h_text_bytes || (n && !h_in))
+        return AGC_HIP_EINVAL;
+    inflate::Walk W;
+    inflate::walk(h_in, n, nullptr, 0, W);
+    *h_n_members = W.n_members;
+    *h_text_bytes = W.text_bytes;
+    return W.why == inflate::W_OK ? AGC_HIP_OK : AGC_HIP_EINVAL;
+}
+
+int agc_hip_bgzf_inflate(agc_hip_ctx *c, const uint8_t *h_in, uint64_t n, uint8_t *h_out, uint64_t out_cap, uint64_t *h_out_len, uint64_t *h_text_off, uint32_t *h_status)
+{
+    return bgzf_inflate_impl(c, h_in, n, h_out, nullptr, out_cap, h_out_len, h_text_off, h_status);
+}
+
+int agc_hip_bgzf_inflate_dev(agc_hip_ctx *c, const uint8_t *h_in, uint64_t n, uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_len, uint64_t *h_text_off, uint32_t *h_status)
+{
+    return bgzf_inflate_impl(c, h_in, n, nullptr, d_out, out_cap, h_out_len, h_text_off, h_status);
 }
 
 int agc_hip_sample_fasta_parts_bgzf(agc_hip_ctx *c, uint32_t n_parts, const agc_hip_part *h_parts, const uint8_t *h_src, uint64_t src_bytes, uint32_t seq_cap, uint32_t n_ctg,

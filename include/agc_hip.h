@@ -67,7 +67,8 @@ enum {
     AGC_HIP_K_PARTS_UNPACK = 16, /* agc_hip_parts_unpack*, agc_hip_sample_fasta_parts*: pack_index_kernel, tuples_size_kernel, tuples_unpack_kernel (parts_unpack_kernels.hip) */
     AGC_HIP_K_RANGES = 17,       /* agc_hip_lz_decode_window_batch*, agc_hip_ranges_parts*: lz_decode_window_kernel, segment_window_kernel, letters_kernel (range_kernels.hip) */
     AGC_HIP_K_BGZF = 18,         /* agc_hip_bgzf*, agc_hip_sample_fasta_parts_bgzf*: bgzf_block_kernel, bgzf_place_kernel (bgzf_kernels.hip) */
-    AGC_HIP_K_COUNT = 19
+    AGC_HIP_K_INFLATE = 19,      /* agc_hip_bgzf_inflate*: bgzf_inflate_kernel (inflate_kernels.hip) */
+    AGC_HIP_K_COUNT = 20
 };
 int agc_hip_timing_enable(agc_hip_ctx *ctx, int on);
 int agc_hip_timing_reset(agc_hip_ctx *ctx);
@@ -644,6 +645,40 @@ int agc_hip_sample_fasta_parts_bgzf_dev(agc_hip_ctx *ctx, uint32_t n_parts, cons
                                         uint32_t n_ctg, const uint64_t *h_ctg_seg, const agc_hip_seg_part *h_seg, uint32_t k, uint32_t min_match_len,
                                         uint32_t line_length, const char *h_names, const uint64_t *h_name_off, uint8_t *d_gz, uint64_t gz_cap, uint64_t *h_gz_len,
                                         uint64_t *h_text_len, uint64_t *h_block_off);
+
+/* BGZF back into its bytes: the stream of agc_hip_bgzf, of `bgzip`, of htslib.  The host walks the stream from byte 0 -- every
+ * member's gzip header with its BC subfield (BSIZE), its trailer (CRC-32, ISIZE <= 65536) -- without inflating anything; the device
+ * then inflates every member with a wavefront of its own (RFC 1951 in full: stored, fixed and dynamic blocks, matches) and checks
+ * its size and CRC-32 (what is decoded and what is refused, check by check: agc_amd/csrc/inflate.h).  A stream is any number of
+ * members back to back; the 28-byte EOF member is a member of 0 bytes and may be missing.  So a slice of a stream that begins and
+ * ends on member boundaries -- cut with the h_block_off of agc_hip_bgzf, or a .gzi -- is a stream, and inflates to its slice of the
+ * text.
+ *
+ * agc_hip_bgzf_members: the walk alone, no context.  *h_n_members / *h_text_bytes = the members and the sum of their ISIZE; after
+ * AGC_HIP_EINVAL (the walk's first complaint) those of the members in front of the one complained about.
+ * agc_hip_bgzf_inflate: *h_out_len = the text's size; h_text_off (optional): n_members + 1 offsets, member m's bytes are out[h_text_off[m] ..
+ * h_text_off[m+1]); h_status (optional): n_members entries, 0 or AGC_HIP_INF_*.  In this order:
+ *  1. The walk.  AGC_HIP_EINVAL at its first complaint, nothing launched: h_status[m] = 0 for the members in front, the complaint
+ *     for member m itself (so h_status holds one entry more than agc_hip_bgzf_members counted, n / 26 + 1 at most); *h_out_len and
+ *     h_text_off cover the members in front.  UNSUPPORTED: CM != 8, reserved FLG bits, no BC subfield (plain gzip).  MALFORMED: a
+ *     truncated header or trailer, BSIZE + 1 smaller than header + trailer or past the input, ISIZE > 65536, bytes behind the last
+ *     member that are no member.
+ *  2. AGC_HIP_ECAP: out_cap is smaller than *h_out_len; nothing was launched or written.
+ *  3. The members are inflated.  AGC_HIP_EINVAL: at least one has a status != 0 (the error text names the first); the members with
+ *     status 0 are complete and correct, the range of a refused member has unspecified contents, no byte outside the members'
+ *     ranges is written.  AGC_HIP_OK: every member has status 0.
+ * n == 0: AGC_HIP_OK, *h_out_len = 0.  Runs on the context's first stream. */
+enum {
+    AGC_HIP_INF_OK = 0,
+    AGC_HIP_INF_UNSUPPORTED = 1, /* a gzip member that is not BGZF: no BC subfield, another method, reserved flags */
+    AGC_HIP_INF_MALFORMED = 2    /* not a member, or a payload that is no deflate stream of ISIZE bytes with that CRC-32 */
+};
+int agc_hip_bgzf_members(const uint8_t *h_in, uint64_t n, uint64_t *h_n_members, uint64_t *h_text_bytes);
+int agc_hip_bgzf_inflate(agc_hip_ctx *ctx, const uint8_t *h_in, uint64_t n, uint8_t *h_out, uint64_t out_cap, uint64_t *h_out_len, uint64_t *h_text_off,
+                         uint32_t *h_status);
+/* the same, the bytes left in device memory (d_out: out_cap bytes the caller owns, any alignment) */
+int agc_hip_bgzf_inflate_dev(agc_hip_ctx *ctx, const uint8_t *h_in, uint64_t n, uint8_t *d_out, uint64_t out_cap, uint64_t *h_out_len, uint64_t *h_text_off,
+                             uint32_t *h_status);
 
 /* One window of a batch of contig ranges: the segment as agc_hip_seg_part names it, and the symbols [win_from, win_from + win_len)
  * of its ORIENTED form (win_len >= 1, win_from + win_len <= length).  The k-symbol overlap between segments is the caller's to
