@@ -13,6 +13,7 @@ from agc_amd import capi
 from tests import collections as COLL
 from tests import lzdec_cases
 from tests import ranges_cases as RC
+from tests import readfuzz_cases as RF
 
 pytestmark = pytest.mark.gpu
 
@@ -133,42 +134,11 @@ def written(tmp_path_factory):
     return out
 
 
-def batch_of(host, rd, seed):
-    """a range inside the first segment of every kind and orientation, the boundary ranges of three contigs (those with the most
-    segments), 200 seeded random ranges of 1 - 3 000 symbols across all samples -> (queries, the (kind, rc) pairs the batch has a
-    window in, those the archive has in segments that keep a symbol)"""
-    k = host.GetParams()["k"]
-    ctgs, in_archive, queries = [], set(), []
-    for s in host.ListSample():
-        plan = host.GetSamplePlan(s)
-        for c, name in enumerate(host.ListCtg(s)):
-            lo, hi = int(plan["ctg_seg"][c]), int(plan["ctg_seg"][c + 1])
-            lens = plan["length"][lo:hi].tolist()
-            ctgs.append((len(lens), s, name, lens, sum(lens) - k * (len(lens) - 1)))
-            pos = 0
-            for i, n in enumerate(lens):  # the first segment of every kind and orientation that keeps a symbol: a range inside it
-                kept = n - (k if i else 0)
-                pair = (int(plan["kind"][lo + i]), int(plan["rc"][lo + i]))
-                if kept > 0 and pair not in in_archive:
-                    in_archive.add(pair)
-                    queries.append((s, name, pos + kept // 3, pos + kept - 1 - kept // 3))
-                pos += kept
-    for _n, s, name, lens, _len in sorted(ctgs, key=lambda x: -x[0])[:3]:
-        queries += [(s, name, f, t) for f, t in RC.contig_ranges(lens, k)]
-    rng = np.random.default_rng(seed)
-    for _ in range(200):
-        _n, s, name, _lens, n = ctgs[int(rng.integers(len(ctgs)))]
-        f = int(rng.integers(max(n, 1)))
-        queries.append((s, name, f, f + int(rng.integers(1, 3001)) - 1))
-    p = host.GetRangeParts(queries)
-    return queries, set(zip(p["kind"].tolist(), p["rc"].tolist())), in_archive
-
-
 def check_reader(ctx, path, base, seed, must_have=()):
     from agc_amd import devread, reader
     host = reader.CAGCFile()
     assert host.Open(path)
-    queries, in_batch, in_archive = batch_of(host, reader, seed)
+    queries, in_batch, in_archive = RF.queries(host, seed)
     # the condition on the inputs: a window in every kind x orientation the archive has
     assert in_batch == in_archive and in_archive >= set(must_have), (sorted(in_batch), sorted(in_archive))
     want = [host.GetCtgSeq(s, name, f, t).encode() for s, name, f, t in queries]
